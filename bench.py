@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- reads/s of the clustering hot path on N MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config3] [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path (pack -> collapse -> bucket pair search ->
 components -> dissection -> kept read ids) over one batch of synthetic keys that
 already sit in HBM. Prints ONE JSON line (rank 0). See DESIGN.md "measurement".
+
+A plain run does what `value` needs and no more: context, input, the context's first job, W warm-up
+steps, K timed steps, the result line. `--full` adds everything else the benchmark measures or checks
+(per-kernel table and roofline from survey steps, the event pair of the dominant kernel in the timed
+steps, PMC traffic, device-copy peak, PCIe-inclusive steps, the CPU baseline with its parity gate, the
+phase table of a sharded step). `--dump-outputs DIR` writes what the last timed step returned.
 """
 from __future__ import annotations
 
@@ -156,7 +162,7 @@ def pmc_traffic(kernel_substr: str, workload: str, reads_per_gpu: int):
         out = tempfile.mkdtemp(prefix=f"fqd_pmc_{counter}_", dir="/tmp")
         cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out, "--",
                sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
-               "--workload", workload, "--no-cpu-baseline", "--no-pmc", "--no-host-input", "--no-copy-peak"]
+               "--workload", workload, "--full", "--no-cpu-baseline", "--no-pmc", "--no-host-input", "--no-copy-peak"]
         if reads_per_gpu:
             cmd += ["--reads-per-gpu", str(reads_per_gpu)]
         env = dict(os.environ, TMPDIR="/tmp")
@@ -253,6 +259,29 @@ def launch_ranks(n_ranks: int, script: str = None, argv=None) -> int:
     return max((abs(c) for c in codes), default=0)
 
 
+DUMP_IDS = 4_000_000      # kept ids written by --dump-outputs at the most (32 MB as float64)
+
+
+def dump_outputs(dirname: str, res, sharded: bool, rank: int, world: int):
+    """What the caller of the last timed step received, as float64 .npy files (ids below 2^53 are exact):
+    counters.npy = [n_unique, n_edges, n_clusters, n_kept, ids listed by this rank, their sum mod 2^48], and
+    kept_read_ids.npy = the ascending kept read ids of this rank -- all of them up to DUMP_IDS, beyond that the
+    ids at DUMP_IDS positions of the list drawn once from a fixed seed (ascending). Ranks above 0 of a
+    multi-GPU run write <name>_rank<r>.npy."""
+    import numpy as np
+    kept = res.kept_read_ids if sharded else res.kept_read_ids[:res.n_kept]
+    listed = int(kept.shape[0])
+    counters = np.array([res.n_unique, res.n_edges, res.n_clusters, res.n_kept, listed,
+                         int(kept.sum().item()) % (1 << 48)], dtype=np.float64)
+    if listed > DUMP_IDS:
+        at = torch.randint(0, listed, (DUMP_IDS,), generator=torch.Generator().manual_seed(0)).sort().values
+        kept = kept[at.to(kept.device)]
+    suffix = f"_rank{rank}" if world > 1 and rank else ""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, f"counters{suffix}.npy"), counters)
+    np.save(os.path.join(dirname, f"kept_read_ids{suffix}.npy"), kept.cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -262,6 +291,12 @@ def main():
     ap.add_argument("--reads-per-gpu", type=int, default=0, help="override the workload's n (testing)")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="reads of the CPU baseline's sample (default: 4 M for keys up to 100 nt, 1 M above)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: survey steps (per-kernel table, roofline), kernel timers, "
+                         "PMC traffic, device-copy peak, PCIe-inclusive steps, the CPU baseline with its parity gate; "
+                         "the --no-* and --kernel-timers options below select among these and need --full")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the multi-GPU code path even with one rank (diagnostic)")
@@ -338,16 +373,18 @@ def main():
     step()
     fence()
     t_first_call_ms = (time.perf_counter() - t_cold0) * 1e3
-    ctx.set_timing(True, None)
-    ctx.kernel_times(reset=True)
-    for _ in range(SURVEY):
-        res = step()
-    fence()
-    kern = {k: [kms, kl] for k, (kms, kl) in ctx.kernel_times(reset=True).items()}
-    per_step = {k: max(1, round(v[1] / SURVEY)) for k, v in kern.items()}      # launches of each kernel in one step
-    stage_sum = {k: v * args.steps for k, v in ctx.stage_times()[0].items()}      # (of the last survey step)
-    dominant = max((k for k in kern if kern[k][1]), key=lambda k: kern[k][0] / kern[k][1], default=kern_names[0])
-    timed_kernels = {"all": None, "dominant": (dominant,), "none": ()}[args.kernel_timers]
+    timed_kernels = ()          # a plain run: no survey, no event pair in the timed steps
+    if args.full:
+        ctx.set_timing(True, None)
+        ctx.kernel_times(reset=True)
+        for _ in range(SURVEY):
+            res = step()
+        fence()
+        kern = {k: [kms, kl] for k, (kms, kl) in ctx.kernel_times(reset=True).items()}
+        per_step = {k: max(1, round(v[1] / SURVEY)) for k, v in kern.items()}      # launches of each kernel in one step
+        stage_sum = {k: v * args.steps for k, v in ctx.stage_times()[0].items()}      # (of the last survey step)
+        dominant = max((k for k in kern if kern[k][1]), key=lambda k: kern[k][0] / kern[k][1], default=kern_names[0])
+        timed_kernels = {"all": None, "dominant": (dominant,), "none": ()}[args.kernel_timers]
     ctx.set_timing(False, timed_kernels)
     for _ in range(args.warmup):
         step()
@@ -358,18 +395,52 @@ def main():
         res = step()
     fence()
     elapsed = time.perf_counter() - t0
-    # the dominant kernel's event pairs of the TIMED steps (the pool holds 512 pairs; later launches are not
-    # timed -- see launches_timed); every other kernel keeps its survey numbers
-    live = ctx.kernel_times(reset=True)
-    dominant_live = live.get(dominant, (0.0, 0))
-    if dominant_live[1]:
-        kern[dominant] = [dominant_live[0], dominant_live[1]]
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = n_total * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, sharded, rank, world)
+    sh = ctx.shape()
+    out = {
+        "metric": "reads/sec clustered (Hamming<=1, 150 bp)", "value": round(value, 1), "unit": "reads/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
+        "timed_region": "t_dev: key bytes resident in HBM -> ascending kept read ids resident in HBM "
+                        "(value = reads / t_dev); t_e2e (pageable host keys -> host ids, PCIe-inclusive) is "
+                        "reported by --full as t_e2e_ms / host_input and is never `value`",
+        "t_dev_ms": round(ms_per_step, 3),
+        "t_first_call_ms": round(t_first_call_ms, 3), "t_context_create_ms": round(t_context_create_ms, 3),
+        "t_first_call_note": "the first job of the fresh context, keys resident in HBM: workspace allocations and first "
+                             "use of every kernel included (fqd_create itself: t_context_create_ms); later jobs of "
+                             "the context reuse the workspace -- t_dev_ms",
+        "data": "synthetic keys generated in HBM (fqd_synth_keys, fastqdedup_amd/synth.py)",
+        "config": {"workload": wl["name"], "reads_per_gpu": n, "reads_total": n_total, "key_len": L,
+                   "max_distance": wl["d"], "metric": "edit" if wl["edit"] else "hamming",
+                   "dissection": wl["method"], "seed": wl["seed"],
+                   "parallelism": (f"1 process/GPU over RCCL, plan {res.plan} (fastqdedup_amd/sharded.py)"
+                                   if sharded else "single GPU")},
+        "result": {"n_unique": res.n_unique, "n_edges": res.n_edges, "n_clusters": res.n_clusters,
+                   "n_kept": res.n_kept},
+        "record_bytes": sh.stride_words * 4, "planes": sh.planes,
+        "route": getattr(res, "route", None),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if sharded:
+            dist.destroy_process_group()
+        return
+
+    # ---- everything below: --full only ------------------------------------------------------------------------
+    # the dominant kernel's event pairs of the TIMED steps (the pool holds 512 pairs; later launches are not
+    # timed -- see launches_timed); every other kernel keeps its survey numbers
+    live = ctx.kernel_times(reset=True)
+    dominant_live = live.get(dominant, (0.0, 0))
+    if dominant_live[1]:
+        kern[dominant] = [dominant_live[0], dominant_live[1]]
     # one more, UNTIMED step with a device sync after every phase: where a sharded step spends its time
     phases = None
     if sharded:
@@ -380,7 +451,6 @@ def main():
     # ---- roofline of the dominant hand-written kernel (DESIGN.md "kernels") --------
     # Every hand-written kernel of the step is timed live with HIP events on the context's stream
     # (fqd_kernel_times). `roofline` is the one with the longest average launch; `kernels` lists all.
-    sh = ctx.shape()
     st = ctx.edge_stats()          # of the last step: all d+1 launches
     nseg = wl["d"] + 1
     b_key = sh.planes * sh.words * 4
@@ -530,41 +600,21 @@ def main():
     # the whole-job fraction SURVEY.md 8d defines, next to the dominant kernel's
     roofline["job"] = {k: job_roofline[k] for k in ("alg_bytes", "achieved", "frac", "traffic")}
 
-    out = {
-        "metric": "reads/sec clustered (Hamming<=1, 150 bp)", "value": round(value, 1), "unit": "reads/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
-        "timed_region": "t_dev: key bytes resident in HBM -> ascending kept read ids resident in HBM "
-                        "(value = reads / t_dev); t_e2e (pageable host keys -> host ids, PCIe-inclusive) is "
-                        "reported as t_e2e_ms / host_input and is never `value`",
-        "t_dev_ms": round(ms_per_step, 3), "t_e2e_ms": None if pcie is None else pcie["ms"],
-        "t_first_call_ms": round(t_first_call_ms, 3), "t_context_create_ms": round(t_context_create_ms, 3),
-        "t_first_call_note": "the first job of the fresh context, keys resident in HBM: workspace allocations and first "
-                             "use of every kernel included (fqd_create itself: t_context_create_ms); later jobs of "
-                             "the context reuse the workspace -- t_dev_ms",
+    out.update({
+        "t_e2e_ms": None if pcie is None else pcie["ms"],
         "t_e2e_pinned_ms": None if pcie is None else pcie.get("pinned_input", {}).get("ms"),
-        "data": "synthetic keys generated in HBM (fqd_synth_keys, fastqdedup_amd/synth.py)",
-        "config": {"workload": wl["name"], "reads_per_gpu": n, "reads_total": n_total, "key_len": L,
-                   "max_distance": wl["d"], "metric": "edit" if wl["edit"] else "hamming",
-                   "dissection": wl["method"], "seed": wl["seed"],
-                   "parallelism": (f"1 process/GPU over RCCL, plan {res.plan} (fastqdedup_amd/sharded.py)"
-                                   if sharded else "single GPU")},
-        "result": {"n_unique": res.n_unique, "n_edges": res.n_edges, "n_clusters": res.n_clusters,
-                   "n_kept": res.n_kept},
         "stage_ms_per_step": {k: round(v / args.steps, 3) for k, v in stage_sum.items()},
-        "record_bytes": sh.stride_words * 4, "planes": sh.planes,
         "dedupe_record_bytes": 12 if compact_records else sh.stride_words * 4,
         "roofline": roofline,
         "job_roofline": job_roofline,
         "kernels": kernels,
-        "route": getattr(res, "route", None),
         "kernel_timers": {"timed_steps": args.kernel_timers, "dominant": dominant_name,
                           "note": "HIP event pairs around every kernel launch stop the stream at each record (~0.12 ms of "
                                   "a config-3 step): the timed steps carry the pair of the dominant kernel only -- "
                                   "roofline.avg_launch_ms is measured there, live -- and the other kernels' numbers come "
                                   f"from {SURVEY} untimed survey steps with all pairs on"},
         "host_input": pcie,
-    }
+    })
     if phases is not None:
         out["sharded_phases_ms_rank0"] = phases
     if rank == 0 and world == 1 and not args.no_cpu_baseline:

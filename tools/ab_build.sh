@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 src=$1; shift
 run() {
-    python bench.py ${BENCH_ARGS:---steps 30 --warmup 8} --no-pmc --no-cpu-baseline --no-host-input --no-copy-peak 2>/dev/null | tail -1 |
+    python bench.py --full ${BENCH_ARGS:---steps 30 --warmup 8} --no-pmc --no-cpu-baseline --no-host-input --no-copy-peak 2>/dev/null | tail -1 |
         python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1'.ljust(40), d['ms_per_step'], {k['kernel'].replace('_kernel','')[:22]: k['ms_per_step'] for k in d['kernels'][:8]})"
 }
 run default

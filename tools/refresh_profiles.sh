@@ -10,28 +10,28 @@ OUT=gpurun_out/profiles_$R
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ "$PART" = "bench1" ] || [ "$PART" = "all" ]; then
-python3 bench.py > $OUT/${R}_bench_config3.json 2> $OUT/bench_config3.err || exit 1
+python3 bench.py --full > $OUT/${R}_bench_config3.json 2> $OUT/bench_config3.err || exit 1
 echo "config3 done"
 # the long-key shapes WITH the PMC passes (job_roofline.traffic), config 5 / 5v without (their child passes take minutes)
 for w in config2 config4; do
-    python3 bench.py --workload $w > $OUT/${R}_bench_$w.json 2> $OUT/bench_$w.err || exit 1
+    python3 bench.py --full --workload $w > $OUT/${R}_bench_$w.json 2> $OUT/bench_$w.err || exit 1
     echo "$w done"
 done
 fi
 if [ "$PART" = "bench2" ] || [ "$PART" = "all" ]; then
 for w in config5 config5v; do
-    python3 bench.py --workload $w --no-pmc > $OUT/${R}_bench_$w.json 2> $OUT/bench_$w.err || exit 1
+    python3 bench.py --full --workload $w --no-pmc > $OUT/${R}_bench_$w.json 2> $OUT/bench_$w.err || exit 1
     echo "$w done"
 done
-python3 bench.py --workload config3_skew --no-pmc --steps 5 --warmup 2 > $OUT/${R}_bench_config3_skew.json 2> $OUT/bench_skew.err || exit 1
+python3 bench.py --full --workload config3_skew --no-pmc --steps 5 --warmup 2 > $OUT/${R}_bench_config3_skew.json 2> $OUT/bench_skew.err || exit 1
 echo "config3_skew done"
-python3 bench.py --force-sharded --no-pmc --no-cpu-baseline --no-host-input --warmup 8 > $OUT/${R}_bench_config3_sharded_world1.json 2> $OUT/bench_sharded.err || exit 1
-python3 bench.py --force-sharded --workload config4 --steps 10 --warmup 3 --no-pmc --no-cpu-baseline --no-host-input > $OUT/${R}_bench_config4_sharded_world1.json 2> $OUT/bench_sharded4.err || exit 1
+python3 bench.py --full --force-sharded --no-pmc --no-cpu-baseline --no-host-input --warmup 8 > $OUT/${R}_bench_config3_sharded_world1.json 2> $OUT/bench_sharded.err || exit 1
+python3 bench.py --full --force-sharded --workload config4 --steps 10 --warmup 3 --no-pmc --no-cpu-baseline --no-host-input > $OUT/${R}_bench_config4_sharded_world1.json 2> $OUT/bench_sharded4.err || exit 1
 echo "sharded done"
 # the skewed model: adjacency, and at distance 2 beside the uniform job of that shape (no CPU baseline: the oracle's
 # quadratic dissection of the 65 536-key component takes minutes at d = 2)
-python3 bench.py --workload config3_skew_adj --no-pmc --steps 5 --warmup 2 --no-cpu-baseline --no-host-input > $OUT/${R}_bench_config3_skew_adj.json 2> $OUT/bench_skew_adj.err || exit 1
-python3 bench.py --workload config4_skew --no-pmc --steps 5 --warmup 2 --no-cpu-baseline --no-host-input > $OUT/${R}_bench_config4_skew.json 2> $OUT/bench_skew4.err || exit 1
+python3 bench.py --full --workload config3_skew_adj --no-pmc --steps 5 --warmup 2 --no-cpu-baseline --no-host-input > $OUT/${R}_bench_config3_skew_adj.json 2> $OUT/bench_skew_adj.err || exit 1
+python3 bench.py --full --workload config4_skew --no-pmc --steps 5 --warmup 2 --no-cpu-baseline --no-host-input > $OUT/${R}_bench_config4_skew.json 2> $OUT/bench_skew4.err || exit 1
 echo "skew variants done"
 hipcc --offload-arch=gfx950 -O3 -o /tmp/mb tools/microbench_patterns.hip 2> /dev/null && /tmp/mb > $OUT/${R}_microbench_patterns.json || exit 1
 echo "microbench done"
