@@ -653,7 +653,8 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
         c->route |= FQD_ROUTE_PASS0_CONTINUED;
     }
     if (!c->search_is_retry)
-        c->route &= ~(FQD_ROUTE_SEARCH_GROUPED | FQD_ROUTE_SEARCH_SORT | FQD_ROUTE_SEARCH_EDIT | FQD_ROUTE_SEARCH_RETRIED);
+        c->route &= ~(FQD_ROUTE_SEARCH_GROUPED | FQD_ROUTE_SEARCH_SORT | FQD_ROUTE_SEARCH_EDIT | FQD_ROUTE_SEARCH_RETRIED |
+                      FQD_ROUTE_SEARCH_SMALL);
     if (!grouped_first && !pass0_held) {
         FQD_TRY(zero_ctr64(c, C64_EDGES));
         HIP_TRY(c, hipMemsetAsync(c->d_stats.p, 0, FQD_STAT_SLOTS * sizeof(fqd::PairStats), c->st));
@@ -670,6 +671,7 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
         // length share the empty segment's bucket), just quadratic.
         const uint32_t d = (uint32_t)max_distance;
         const uint32_t nseg = d + 1;
+        // (+ 16: the small search reads its rows as whole uint4, launch_small_search)
         HIP_TRY(c, c->seg_hashes.reserve((size_t)(seg_hi - seg_lo) * U * 4 + 16));
         HIP_TRY(c, c->sorted_hash.reserve(U * 4 + 16));
         HIP_TRY(c, c->sorted_uid.reserve(U * 4 + 16));
@@ -698,6 +700,13 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
         const char *pin = getenv("FQD_EDGES");
         bool grouped = n_shards == 1 && U < 0xFFFFFF00ull && (pin ? !strcmp(pin, "grouped") : U >= 65536) &&
                        !c->search_force_sort;
+        // A table under 65 536 keys (FQD_EDGES=small: any table): every pass in one launch, grouped in LDS
+        // (small_search.hip). A segment value shared by more keys than a workgroup holds raises C64_CAND_NEED
+        // (unused off the grouped path) and the search runs again on the sort path. Not behind a routed collapse that has
+        // done pass 0 (pass0_held): that fall-back clears the edge counter, and pass 0's edges with it.
+        bool small = n_shards == 1 && !grouped && !pass0_held && !c->search_force_sort && U < 0xFFFFFF00ull &&
+                     (pin ? !strcmp(pin, "small") : U < 65536);
+        const uint32_t small_cap = fqd::small_search_cap();
         // Candidate pairs are listed before they are verified; a segment value shared by very many
         // keys (all of them pairwise candidates) would need a list beyond this budget: the search
         // then runs again on the sort path, which verifies in place and needs no list.
@@ -719,7 +728,14 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
                                  (uint64_t)n_pass * U < 0xFFFFFF00ull && !getenv("FQD_GROUP_NO_FUSED_PASSES");
         bool used_refine = false;
         for (int attempt = 0;; attempt++) {
-            c->route |= (grouped ? FQD_ROUTE_SEARCH_GROUPED : FQD_ROUTE_SEARCH_SORT) | (attempt ? FQD_ROUTE_SEARCH_RETRIED : 0u);
+            c->route |= (grouped ? FQD_ROUTE_SEARCH_GROUPED : small ? FQD_ROUTE_SEARCH_SMALL : FQD_ROUTE_SEARCH_SORT) |
+                        (attempt ? FQD_ROUTE_SEARCH_RETRIED : 0u);
+            if (small && seg_hi > seg_lo)
+                KTIME(c, FQD_K_PAIRS, fqd::launch_small_search(
+                               c->seg_hashes.as<uint32_t>(), seg_hi - seg_lo, U, c->urecs.as<uint32_t>(),
+                               c->ulens.as<uint32_t>(), c->ks, d, seg_lo, nseg, c->edges.as<uint32_t>(),
+                               c->d_ctr64.as<unsigned long long>() + C64_EDGES, c->edge_cap,
+                               c->d_ctr64.as<unsigned long long>() + C64_CAND_NEED, c->d_stats.as<fqd::PairStats>(), c->st));
             if (fuse_passes && grouped) {
                 FQD_TRY(grouped_pass(c, c->seg_hashes.as<uint32_t>(), (uint64_t)n_pass * U, d, seg_lo, nseg, (uint32_t)U));
                 if (c->gp_crowded_bits && (c->gp_tiles || !c->gp_fine_ok) && tiles_possible(c, nseg) &&
@@ -753,7 +769,7 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
                     }
                 }
             }
-            for (uint32_t s = seg_lo; s < seg_hi && !(fuse_passes && grouped); s++) {
+            for (uint32_t s = seg_lo; s < seg_hi && !(fuse_passes && grouped) && !small; s++) {
                 const uint32_t *pass_hashes = c->seg_hashes.as<uint32_t>() + (size_t)(s - seg_lo) * U;
                 uint64_t m = U;  // entries this rank sorts and searches in this pass
                 if (n_shards > 1) {
@@ -807,12 +823,18 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
             }
             // pass 0 by the collapse's compaction, found incomplete now: a bucket of more rows than a wave holds
             const bool pass0_short = pass0_held && taken_u32(c, 0) != 0;
-            if (!slab_over && now <= c->edge_cap && cand_need <= c->gp_cand_cap && !pass0_short) {
+            // a workgroup of the small search met more items than it holds: its pairs are missing
+            const bool small_over = small && ctrs[C64_CAND_NEED] > small_cap;
+            if (!slab_over && now <= c->edge_cap && cand_need <= c->gp_cand_cap && !pass0_short && !small_over) {
                 have = now;
                 break;
             }
             if (attempt > 2)
                 return fail(c, FQD_E_RUNTIME, "edge buffer kept overflowing");
+            if (small_over) {
+                small = false;
+                c->route &= ~FQD_ROUTE_SEARCH_SMALL;
+            }
             if (now > c->edge_cap) {
                 c->edges.release();
                 HIP_TRY(c, c->edges.reserve((size_t)(now + now / 8 + 1024) * 8));

@@ -517,6 +517,14 @@ hipError_t launch_select_shard(const uint32_t *hashes, uint64_t U, uint32_t shar
 hipError_t launch_pairs_within(const uint8_t *a, const uint64_t *ao, const uint8_t *b, const uint64_t *bo,
                                uint64_t n, int d, int metric, uint8_t *out, hipStream_t st);
 
+// small_search.hip -- every pass of the Hamming search of a small table in one launch, grouped in LDS without a sort
+uint32_t small_search_cap();   // items one workgroup holds; *need above it afterwards: a bin overflowed, nothing of the output counts
+// seg_hashes: 16-byte aligned, and readable up to 16 bytes behind its n_pass * U words (the rows are read as whole uint4)
+hipError_t launch_small_search(const uint32_t *seg_hashes /* [n_pass][U], segments seg_lo .. */, uint32_t n_pass, uint64_t U,
+                               const uint32_t *urecs, const uint32_t *ulens, KeyShape sh, uint32_t d, uint32_t seg_lo,
+                               uint32_t nseg, uint32_t *edges, unsigned long long *edge_count, uint64_t edge_cap,
+                               unsigned long long *need /* zeroed by the caller */, PairStats *stats, hipStream_t st);
+
 // edit.hip -- Levenshtein neighbour search + contains
 hipError_t launch_len_present(const uint32_t *ulens, uint64_t U, KeyShape sh, uint8_t *len_present, hipStream_t st);
 hipError_t launch_edit_records(const uint32_t *urecs, const uint32_t *ulens, uint64_t U, KeyShape sh, uint32_t d,

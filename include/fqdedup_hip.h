@@ -102,6 +102,8 @@ typedef struct fqd_summary {
                                             * persistent kernel: no tmp rows between the LDS table and the unique table   */
 #define FQD_ROUTE_SEARCH_TILES    0x10000u /* crowded segment values that the finer segments could not split (a family
                                             * varying inside one piece) were compared ALL PAIRS, tiled over the GPU         */
+#define FQD_ROUTE_SEARCH_SMALL    0x20000u /* neighbour search of a table under 65 536 keys: every pass in ONE launch, the
+                                            * keys grouped by segment hash in LDS tables, no sort (small_search.hip)        */
 int fqd_get_route(const fqd_ctx *ctx, uint32_t *route);
 
 /* Packed-key geometry chosen by fqd_pack_keys (DESIGN.md "data layout"). */
