@@ -69,6 +69,73 @@ int find_edges_edit(fqd_ctx *c, uint32_t d, uint32_t shard, uint32_t n_shards)
     return FQD_OK;
 }
 
+// Tables under this many keys take the small route by themselves (at and above it find_edges_edit_grouped does).
+constexpr uint64_t SMALL_EDIT_MAX_KEYS = 32768;
+
+// The same search for a small table (small_edit_search.hip): an items kernel and a search kernel, one read-back of
+// the counters behind them. d = 1..3, one shard, collapsed or not; FQD_EDIT=small pins it for any table under 2^26
+// keys. *done = false: not applicable, or a bin overflowed (a segment value shared by more items than a workgroup
+// holds) -- the edge counter and the statistics are cleared again and the caller runs the sorted search.
+int find_edges_edit_small(fqd_ctx *c, uint32_t d, uint32_t n_shards, bool *done)
+{
+    *done = false;
+    const uint64_t U = c->U;
+    const KeyShape sh = c->ks;
+    const char *pin = getenv("FQD_EDIT");
+    if (n_shards != 1 || d < 1 || d > 3 || U < 2 || U >= (1ull << 26) || sh.planes > 7 || sh.max_len > fqd::SMALL_EDIT_MAX_LEN)
+        return FQD_OK;
+    if (pin ? strcmp(pin, "small") != 0 : U >= SMALL_EDIT_MAX_KEYS)
+        return FQD_OK;
+    fqd::SmallEdit A = fqd::small_edit_plan(U, sh, d);
+    const size_t n_bins = (size_t)1 << A.nb_bits;
+    HIP_TRY(c, c->ed_cands.reserve(n_bins * A.cap * 8));
+    HIP_TRY(c, c->eg_per_key.reserve(n_bins * 4));
+    // (a table of a few hundred keys -- the dissection of one cluster, where most pairs are edges -- gets room for
+    // all its pairs at once)
+    const uint64_t want = std::max<uint64_t>(std::max<uint64_t>(1024, U), std::min<uint64_t>(U * (U - 1) / 2, 65536));
+    if (c->edge_cap < want || !c->edges.p)
+        HIP_TRY(c, c->edges.reserve(want * 8));
+    c->edge_cap = c->edges.cap / 8;
+    unsigned long long *ctr = c->d_ctr64.as<unsigned long long>();
+    A.urecs = c->urecs.as<uint32_t>();
+    A.ulens = c->ulens.as<uint32_t>();
+    A.slabs = c->ed_cands.as<uint2>();
+    A.fill = c->eg_per_key.as<uint32_t>();
+    A.edge_count = ctr + C64_EDGES;
+    A.need = ctr + C64_CAND_NEED;
+    A.stats = c->d_stats.as<fqd::PairStats>();
+    for (int attempt = 0;; attempt++) {
+        // (find_edges_impl has cleared the edge counter and the statistics)
+        A.edges = c->edges.as<uint32_t>();
+        A.edge_cap = c->edge_cap;
+        HIP_TRY(c, hipMemsetAsync(A.fill, 0, n_bins * 4, c->st));
+        FQD_TRY(zero_ctr64(c, C64_CAND_NEED));
+        HIP_TRY(c, fqd::launch_small_edit_items(A, sh, c->st));
+        KTIME(c, FQD_K_PAIRS, fqd::launch_small_edit_search(A, sh, c->st));
+        unsigned long long ctrs[C64_CAND_NEED + 1] = {0};
+        FQD_TRY(read_ctr64(c, 0, ctrs, C64_CAND_NEED + 1));
+        const unsigned long long now = ctrs[C64_EDGES];
+        const bool over = ctrs[C64_CAND_NEED] > A.cap;
+        if (!over && now <= c->edge_cap) {
+            c->E = now;
+            c->route |= FQD_ROUTE_SEARCH_SMALL_EDIT;
+            c->stats_pending = true;     // the stat slots are summed when fqd_edge_stats asks
+            *done = true;
+            return FQD_OK;
+        }
+        if (attempt > 2)
+            return fail(c, FQD_E_RUNTIME, "edge buffer kept overflowing");
+        c->route |= FQD_ROUTE_SEARCH_RETRIED;
+        FQD_TRY(zero_ctr64(c, C64_EDGES));
+        HIP_TRY(c, hipMemsetAsync(c->d_stats.p, 0, FQD_STAT_SLOTS * sizeof(fqd::PairStats), c->st));
+        if (over)
+            return FQD_OK;
+        c->edges.release();
+        HIP_TRY(c, c->edges.reserve((size_t)(now + now / 8 + 1024) * 8));
+        c->edge_cap = c->edges.cap / 8;
+    }
+}
+
 }  // namespace
 
 extern "C" int fqd_api_partition_pairs(fqd_ctx *c, const uint32_t *keys, uint64_t N, uint32_t B, bool slabs,
@@ -654,17 +721,21 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
     }
     if (!c->search_is_retry)
         c->route &= ~(FQD_ROUTE_SEARCH_GROUPED | FQD_ROUTE_SEARCH_SORT | FQD_ROUTE_SEARCH_EDIT | FQD_ROUTE_SEARCH_RETRIED |
-                      FQD_ROUTE_SEARCH_SMALL);
+                      FQD_ROUTE_SEARCH_SMALL | FQD_ROUTE_SEARCH_SMALL_EDIT);
     if (!grouped_first && !pass0_held) {
         FQD_TRY(zero_ctr64(c, C64_EDGES));
         HIP_TRY(c, hipMemsetAsync(c->d_stats.p, 0, FQD_STAT_SLOTS * sizeof(fqd::PairStats), c->st));
     }
     if (edit_general && U >= 2 && (max_distance > 0 || !c->collapsed)) {
-        bool grouped_done = false;
+        bool grouped_done = false, small_done = false;
         c->route |= FQD_ROUTE_SEARCH_EDIT;
-        if (n_shards == 1 && c->collapsed)
+        // under 32 768 keys (FQD_EDIT=small: any table): items and search in two launches, one read-back; a bin that
+        // overflows sends the search down the sorted way
+        FQD_TRY(find_edges_edit_small(c, (uint32_t)max_distance, n_shards, &small_done));
+        const bool small_over = !small_done && (c->route & FQD_ROUTE_SEARCH_RETRIED);
+        if (!small_done && !small_over && n_shards == 1 && c->collapsed)
             FQD_TRY(find_edges_edit_grouped(c, (uint32_t)max_distance, &grouped_done));
-        if (!grouped_done)
+        if (!small_done && !grouped_done)
             FQD_TRY(find_edges_edit(c, (uint32_t)max_distance, shard, n_shards));
     } else if (U >= 2 && (max_distance > 0 || !c->collapsed)) {
         // with d >= max_len every segment split has empty segments: still correct (all keys of a

@@ -525,6 +525,31 @@ hipError_t launch_small_search(const uint32_t *seg_hashes /* [n_pass][U], segmen
                                uint32_t nseg, uint32_t *edges, unsigned long long *edge_count, uint64_t edge_cap,
                                unsigned long long *need /* zeroed by the caller */, PairStats *stats, hipStream_t st);
 
+// small_edit_search.hip -- the Levenshtein search (d = 1..3) of a small table: an items kernel (index and probe items
+// of every key into per-bin slabs) and a search kernel (one workgroup per bin), no host round trip between them
+constexpr uint32_t SMALL_EDIT_MAX_LEN = (1u << 18) - 1u;   // (the items kernel keeps one bit per possible key length in LDS)
+struct SmallEdit {
+    // small_edit_plan() fills these ...
+    uint32_t U, d;
+    uint32_t nb_bits;                         // 1 << nb_bits bins (top hash bits), a slab and a workgroup each
+    uint32_t cap;                             // items a slab holds
+    uint32_t slots;                           // LDS table slots: a power of two >= 2 * cap
+    uint32_t chain_limit;
+    uint32_t items_per_key;                   // upper bound, see small_edit_plan
+    // ... and the caller these
+    const uint32_t *urecs, *ulens;
+    uint2 *slabs;                             // [1 << nb_bits][cap] (hash, payload)
+    uint32_t *fill;                           // [1 << nb_bits] items filed per bin, zeroed by the caller
+    uint32_t *edges;
+    unsigned long long *edge_count;
+    uint64_t edge_cap;
+    unsigned long long *need;                 // zeroed by the caller; above cap afterwards: a bin overflowed, nothing of the output counts
+    PairStats *stats;
+};
+SmallEdit small_edit_plan(uint64_t U, KeyShape sh, uint32_t d);
+hipError_t launch_small_edit_items(const SmallEdit &A, KeyShape sh, hipStream_t st);
+hipError_t launch_small_edit_search(const SmallEdit &A, KeyShape sh, hipStream_t st);
+
 // edit.hip -- Levenshtein neighbour search + contains
 hipError_t launch_len_present(const uint32_t *ulens, uint64_t U, KeyShape sh, uint8_t *len_present, hipStream_t st);
 hipError_t launch_edit_records(const uint32_t *urecs, const uint32_t *ulens, uint64_t U, KeyShape sh, uint32_t d,

@@ -104,6 +104,8 @@ typedef struct fqd_summary {
                                             * varying inside one piece) were compared ALL PAIRS, tiled over the GPU         */
 #define FQD_ROUTE_SEARCH_SMALL    0x20000u /* neighbour search of a table under 65 536 keys: every pass in ONE launch, the
                                             * keys grouped by segment hash in LDS tables, no sort (small_search.hip)        */
+#define FQD_ROUTE_SEARCH_SMALL_EDIT 0x40000u /* Levenshtein search (d = 1..3) of a table under 32 768 keys: index and probe
+                                            * items into per-bin slabs, one workgroup per bin (small_edit_search.hip)       */
 int fqd_get_route(const fqd_ctx *ctx, uint32_t *route);
 
 /* Packed-key geometry chosen by fqd_pack_keys (DESIGN.md "data layout"). */
