@@ -36,6 +36,29 @@ class Shape(C.Structure):
                 ("alphabet", C.c_uint8 * 128)]
 
 
+FASTQ_MAX_FILES = 8
+FASTQ_LINE_TILE = 4096          # bytes per workgroup of the line index (fastq_ingest.hip FQ_LINE_TILE)
+FASTQ_SCAN_STEP = 1024 * 16     # tile counts one step of the one-workgroup scan takes (prims.hip SS_THREADS * SS_PER)
+FASTQ_IN_TILE = 32 * 1024       # LDS input tile of the gather kernel (fastq_ingest.hip FQ_IN_TILE)
+FASTQ_ERRORS = {1: "Line expected to start with '@'", 2: "Line expected to start with '+'",
+                3: "Length of sequence and qualities differ", 4: "Premature end of file encountered."}
+
+
+class FastqIndexInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("error_line", C.c_uint64), ("max_record_bytes", C.c_uint32),
+                ("error_kind", C.c_int32)]
+
+
+class FastqSlice(C.Structure):
+    _fields_ = [("start", C.c_int64), ("stop", C.c_int64), ("step", C.c_int64)]
+
+
+class FastqAppendInfo(C.Structure):
+    _fields_ = [("key_bytes", C.c_uint64), ("n_discarded", C.c_uint64), ("first_non_mate", C.c_uint64),
+                ("consumed", C.c_uint64 * FASTQ_MAX_FILES), ("name_start", C.c_uint64 * FASTQ_MAX_FILES),
+                ("name_len", C.c_uint32 * FASTQ_MAX_FILES), ("fixed_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # every symbol include/fqdedup_hip.h declares (tests check the library exports them all)
 EXPORTS = [
     "fqd_device_count", "fqd_global_error", "fqd_create", "fqd_destroy", "fqd_last_error",
@@ -49,6 +72,7 @@ EXPORTS = [
     "fqd_store_add_keys", "fqd_store_remove", "fqd_store_removed_count", "fqd_get_clusters", "fqd_read_clusters",
     "fqd_trie_order", "fqd_trie_stats", "fqd_store_symbol_events", "fqd_get_stream", "fqd_pack_collapse", "fqd_synth_indel_keys", "fqd_copy_bandwidth",
     "fqd_synth_keys_skewed", "fqd_get_route", "fqd_cluster_subgraph", "fqd_cluster_subgraph_home", "fqd_dissect_except",
+    "fqd_fastq_begin", "fqd_fastq_index", "fqd_fastq_append", "fqd_fastq_stats",
     "fqd_owner_routing_possible", "fqd_set_owner_routing", "fqd_dense_owner_slabs", "fqd_owner_slab_geometry", "fqd_pack_to_owner_slabs", "fqd_collapse_owner_slabs",
 ]
 
@@ -163,6 +187,12 @@ def load() -> C.CDLL:
     L.fqd_contains.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, C.c_int, vp, C.c_int]
     L.fqd_quality_filter.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, vp, vp, vp,
                                      u64p, C.c_int]
+    L.fqd_fastq_begin.argtypes = [vp, C.c_uint32]
+    L.fqd_fastq_index.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.c_int, C.c_int, C.c_uint64,
+                                  C.POINTER(FastqIndexInfo)]
+    L.fqd_fastq_append.argtypes = [vp, C.c_uint64, vp, C.c_double, vp, C.c_uint32, vp, C.c_uint64, C.c_uint64, vp, vp, vp,
+                                   C.POINTER(FastqAppendInfo)]
+    L.fqd_fastq_stats.argtypes = [vp, u64p]
     L.fqd_stage_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     L.fqd_kernel_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]
     L.fqd_set_timing.argtypes = [vp, C.c_int, C.c_uint32]
@@ -702,6 +732,63 @@ class Context:
                                             fp, mp_, C.byref(nd), mem))
         return flags, means, int(nd.value)
 
+    # ---- FASTQ ingest ------------------------------------------------------------
+    def fastq_begin(self, n_files: int) -> None:
+        self._ck(self._L.fqd_fastq_begin(self._h, int(n_files)))
+
+    def fastq_index(self, file: int, block, n_bytes: Optional[int] = None, *, final: bool = False,
+                    first_line: int = 0) -> FastqIndexInfo:
+        """Index one block of raw FASTQ bytes (numpy uint8 array on the host, or torch uint8 tensor) of file
+        ``file``: complete records, largest record, first format fault (fqd_fastq_index)."""
+        bp, bm, _b = _ptr_mem(block)
+        if n_bytes is None:
+            n_bytes = block.numel() if hasattr(block, "numel") else block.size
+        info = FastqIndexInfo()
+        self._ck(self._L.fqd_fastq_index(self._h, int(file), bp, int(n_bytes), bm, int(bool(final)), int(first_line),
+                                         C.byref(info)))
+        return info
+
+    @staticmethod
+    def _fastq_slices(slices):
+        if slices is None:
+            return None
+        big, small = (1 << 63) - 1, -(1 << 63)
+        clamp = lambda v: max(small, min(big, int(v)))
+        arr = (FastqSlice * len(slices))()
+        for i, sl in enumerate(slices):
+            sl = slice(None) if sl is None else sl
+            step = 1 if sl.step is None else clamp(sl.step)
+            if step == 0:
+                raise ValueError("slice step cannot be zero")
+            arr[i].step = step
+            arr[i].start = (big if step < 0 else 0) if sl.start is None else clamp(sl.start)
+            arr[i].stop = (small if step < 0 else big) if sl.stop is None else clamp(sl.stop)
+        return arr
+
+    def fastq_append(self, n: int, keys_out, key_base: int, offsets_out, weights_out=None, means_out=None, *,
+                     slices=None, threshold: float = 1.0, table=None, phred_offset: int = 33) -> FastqAppendInfo:
+        """Keys, offsets and weights of the first n records of every indexed block into device tensors
+        (fqd_fastq_append): ``offsets_out`` / ``weights_out`` / ``means_out`` start at this chunk's first record."""
+        for t in (keys_out, offsets_out, weights_out, means_out):
+            if t is not None and not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous()):
+                raise ValueError("fastq_append writes into contiguous device tensors")
+        arr = self._fastq_slices(slices)
+        tb = None if table is None else np.ascontiguousarray(table, dtype=np.float64)
+        info = FastqAppendInfo()
+        self._ck(self._L.fqd_fastq_append(
+            self._h, int(n), None if arr is None else C.addressof(arr), float(threshold),
+            None if tb is None else tb.ctypes.data, int(phred_offset), keys_out.data_ptr(),
+            keys_out.numel(), int(key_base), offsets_out.data_ptr(),
+            None if weights_out is None else weights_out.data_ptr(),
+            None if means_out is None else means_out.data_ptr(), C.byref(info)))
+        return info
+
+    def fastq_stats(self) -> dict:
+        """Since fastq_begin: records appended, key bytes written, records discarded, chunks appended."""
+        v = (C.c_uint64 * 4)()
+        self._ck(self._L.fqd_fastq_stats(self._h, v))
+        return {"records": int(v[0]), "key_bytes": int(v[1]), "discarded": int(v[2]), "chunks": int(v[3])}
+
     # ---- the Trie object as a device-resident store ------------------------------
     @staticmethod
     def _alphabet_bytes(alphabet: str) -> np.ndarray:
@@ -792,12 +879,13 @@ class Context:
                "part_scatter_kernel<2>", "bucket_dedupe_kernel", "bucket_compact_kernel", "head_flags_kernel",
                "write_unique_kernel", "segment_hashes_kernel", "bucket_pairs_kernel", "uf_union_kernel",
                "uf_flatten_kernel", "dissect_round_kernel", "gp_hist_kernel", "gp_scatter_kernel", "verify_candidates_kernel", "kept_flags_kernel",
-               "part_scatter12_kernel", "bucket_dedupe12_kernel"]
+               "part_scatter12_kernel", "bucket_dedupe12_kernel", "fastq_line_count_kernel", "fastq_line_scatter_kernel",
+               "fastq_records_kernel", "fastq_mates_kernel", "fastq_key_lens_kernel", "fastq_gather_kernel"]
 
     def kernel_times(self, reset: bool = True):
         """{kernel: (ms summed over launches, launches)} since the last reset."""
-        ms = (C.c_float * 20)()
-        ln = (C.c_uint32 * 20)()
+        ms = (C.c_float * len(self.KERNELS))()
+        ln = (C.c_uint32 * len(self.KERNELS))()
         self._ck(self._L.fqd_kernel_times(self._h, ms, ln, int(reset)))
         return {k: (float(ms[i]), int(ln[i])) for i, k in enumerate(self.KERNELS)}
 

@@ -839,6 +839,7 @@ void fqd_destroy(fqd_ctx *c)
                       &c->eg_per_key_incl, &c->ld_side, &c->ld_side_table};
     for (DevBuf *b : bufs)
         b->release();
+    fqd_api_fastq_release(c);
     if (c->ev_rb)
         (void)hipEventDestroy(c->ev_rb);
     if (c->ev_fork)

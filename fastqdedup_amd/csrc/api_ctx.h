@@ -76,6 +76,15 @@ enum Stage { ST_EMPTY = 0, ST_PACKED = 1, ST_UNIQUE = 2, ST_EDGES = 3, ST_LABELS
 
 // small device-side words read back by the host
 enum Ctr { C_BAD = 0, C_COLLISIONS = 1, C_CHANGED = 2, C_MINLEN = 3, C_MAXLEN = 4, C_PACKBAD = 5, C_SIDE = 6, C_P0 = 7, C_N32 = 8 };
+// one input file of the FASTQ ingest (api_fastq.hip): its current block on the device and the index over it
+struct FastqSlot {
+    DevBuf bytes, nl, tiles, spans, info;
+    const uint8_t *d = nullptr;    // the block: bytes.p, or the caller's device buffer
+    uint64_t n_bytes = 0, n_rec = 0;
+    uint32_t nl_cap = 0, rec_cap = 0, max_rec = 0;
+    bool indexed = false, faulty = false;
+};
+
 enum Ctr64 { C64_EDGES = 0, C64_ROOTS = 1, C64_SUM = 2, C64_STATS = 3, C64_CANDS = 4, C64_CAND_NEED = 5, C64_SLAB = 6, C64_UF_AGAIN = 7, C64_N = 8 };
 
 }  // namespace
@@ -194,6 +203,13 @@ struct fqd_ctx {
     // the unique table as a store (fqd_store_*): rows removed since the last merge, ids handed out
     DevBuf store_alive, st_recs, st_lens, st_counts, st_first, st_comb_recs, st_comb_lens, st_comb_w, st_comb_ids;
     uint64_t store_removed = 0, store_table_U = 0, store_next_id = 0;
+    // FASTQ ingest (api_fastq.hip)
+    FastqSlot fq[fqd::FQ_MAX_FILES];
+    uint32_t fq_files = 0;
+    DevBuf fq_lens, fq_incl, fq_ctr, fq_table;
+    double fq_table_host[128];     // what fq_table holds (fq_table_valid)
+    bool fq_table_valid = false;
+    uint64_t fq_records = 0, fq_key_bytes = 0, fq_discarded = 0, fq_chunks = 0;   // since fqd_fastq_begin
     // scratch
     DevBuf tmp, stage_a, stage_b, stage_c, stage_d;
     DevBuf span;                   // fqd_cluster_subgraph_home: one byte per node, 1 = its cluster has keys on two ranks
@@ -524,6 +540,7 @@ int fqd_api_flat_labels(fqd_ctx *c);                       // api_graph.hip
 // the collapse over c->recs with DEVICE weights and ids (api.hip)
 int fqd_api_collapse_device(fqd_ctx *c, const uint32_t *d_weights, IdSource ids, uint64_t id_limit, uint64_t *n_unique);
 int fqd_api_graph_preinit(fqd_ctx *c, int method);          // api_graph.hip
+void fqd_api_fastq_release(fqd_ctx *c);                     // api_fastq.hip
 extern "C" int fqd_api_partition_pairs(fqd_ctx *c, const uint32_t *keys, uint64_t N, uint32_t B, bool slabs,
                                        const uint32_t **items_out, const uint32_t **bucket_end_out,
                                        const uint32_t *values);   // api_search.hip

@@ -812,4 +812,45 @@ hipError_t launch_synth_indels(uint64_t n_total, uint64_t start, uint64_t count,
                                uint64_t seed, uint32_t copies, uint64_t thr_n, uint64_t thr_sub, uint64_t thr_indel,
                                unsigned long long *lens, const unsigned long long *offsets, uint8_t *out, hipStream_t st);
 
+// fastq_ingest.hip -- raw FASTQ bytes to keys, offsets and weights
+constexpr uint32_t FQ_MAX_FILES = 8;
+constexpr uint32_t FQ_LINE_TILE = 4096;     // bytes a workgroup of the line index takes
+// per-record words the record kernel writes, field k at spans[k * rec_cap + record]
+enum FastqSpan { FQS_SEQ_START = 0, FQS_SEQ_LEN, FQS_QUAL_START, FQS_ID_START, FQS_ID_WORD, FQS_NAME_LEN, FQS_REC_END };
+constexpr uint32_t FQ_SPAN_FIELDS = 7;
+// the 64-bit words of one file's index (read back in one copy) and the kinds of its error word (line << 2 | kind)
+enum FastqIndexWord { FQI_ERROR = 0, FQI_RECORDS = 1, FQI_MAX_RECORD = 2, FQI_NEWLINES = 3, FQI_WORDS = 4 };
+enum FastqError { FQ_ERR_AT = 0, FQ_ERR_PLUS = 1, FQ_ERR_LENGTHS = 2, FQ_ERR_PREMATURE = 3 };
+// the 32-bit words of one append (read back in one copy)
+enum FastqCounter { FQC_MIN_LEN = 0, FQC_MAX_LEN, FQC_MATE, FQC_DISCARDED, FQC_BAD, FQC_OVERFLOW, FQC_KEY_BYTES, FQC_PAD,
+                    FQC_CONSUMED, FQC_WORDS = FQC_CONSUMED + FQ_MAX_FILES };
+struct FastqSlice {
+    long long start, stop, step;     // a Python slice with None replaced by the extreme values CPython uses
+};
+struct FastqFiles {
+    const uint8_t *bytes[FQ_MAX_FILES];
+    const uint32_t *spans[FQ_MAX_FILES];
+    uint64_t n_bytes[FQ_MAX_FILES];
+    uint32_t rec_cap[FQ_MAX_FILES];
+    FastqSlice slice[FQ_MAX_FILES];
+    uint32_t n_files;
+};
+uint32_t fastq_line_tiles(uint64_t n_bytes);
+hipError_t launch_fastq_line_count(const uint8_t *bytes, uint64_t n_bytes, uint32_t *tile_count, unsigned long long *info,
+                                   hipStream_t st);
+hipError_t launch_fastq_line_scatter(const uint8_t *bytes, uint64_t n_bytes, const uint32_t *tile_incl, uint32_t *nl,
+                                     uint32_t nl_cap, hipStream_t st);
+hipError_t launch_fastq_records(const uint8_t *bytes, uint64_t n_bytes, const uint32_t *nl, const uint32_t *tile_incl,
+                                uint32_t nl_cap, int final, uint32_t *spans, uint32_t rec_cap, unsigned long long *info,
+                                hipStream_t st);
+hipError_t launch_fastq_counters_init(uint32_t *ctr, hipStream_t st);
+hipError_t launch_fastq_mates(const FastqFiles &files, uint32_t n, uint32_t *ctr, hipStream_t st);
+hipError_t launch_fastq_key_lens(const FastqFiles &files, uint32_t n, uint32_t *lens, uint32_t *ctr, hipStream_t st);
+// records per workgroup of the gather kernel, from the largest record of every file
+uint32_t fastq_gather_records(const uint32_t *max_record, uint32_t n_files);
+hipError_t launch_fastq_gather(const FastqFiles &files, uint32_t n, uint32_t R, const uint32_t *incl, const double *table,
+                               uint32_t phred_offset, uint32_t max_score, double threshold, int do_quality,
+                               uint8_t *keys_out, uint64_t keys_capacity, uint64_t key_base, uint64_t *offsets_out,
+                               uint32_t *weights_out, double *means_out, uint32_t *ctr, hipStream_t st);
+
 }  // namespace fqd

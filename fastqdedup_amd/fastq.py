@@ -317,6 +317,141 @@ def build_strings(tables: Sequence[FastqTable], slices: Optional[Sequence[Option
 
 
 # ---------------------------------------------------------------------------
+# pass 1 on the device
+# ---------------------------------------------------------------------------
+
+class _HostBlock:
+    """The bytes of one file that the device has not consumed yet, in page-locked memory (the copy to the
+    device then runs at the link's rate and needs no staging copy)."""
+
+    def __init__(self, size: int):
+        self._alloc(size)
+        self.fill, self.eof = 0, False
+
+    def _alloc(self, size: int):
+        import torch
+        self.t = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+        self.a = self.t.numpy()
+
+    def read(self, fh, want: int) -> None:
+        if self.fill + want > len(self.a):
+            old = self.a
+            self._alloc(max(self.fill + want, 2 * len(old)))
+            self.a[: self.fill] = old[: self.fill]
+        view, end = memoryview(self.a), self.fill + want
+        while self.fill < end:
+            got = fh.readinto(view[self.fill:end])
+            if not got:
+                self.eof = True
+                break
+            self.fill += got
+
+    def drop(self, consumed: int) -> None:
+        rest = self.fill - consumed
+        if consumed and rest:
+            self.a[:rest] = self.a[consumed:self.fill]
+        self.fill = rest
+
+
+class DeviceIngest:
+    """Pass 1 of ``deduplicate_cluster`` with the parsing on the device: what ``zip_chunks`` + ``check_mates`` +
+    ``build_strings`` + the quality gate do on the host (reference __init__.py:54-57, :160-167, :180-185, :243-251).
+    The host reads a block of every file (``FQD_FASTQ_BLOCK_BYTES``, default 64 MiB), the device indexes it
+    (``Context.fastq_index``) and appends the keys, offsets and weights of the records every file has complete
+    (``Context.fastq_append``) to torch tensors that grow geometrically; what a block holds behind its last
+    consumed record is carried over to the next one. Stops with the shortest file. After ``run()``:
+    ``keys`` / ``offsets`` / ``weights`` (/ ``means``) hold ``key_bytes`` bytes and ``n`` records, ``key_len`` is
+    the key length when every chunk reported the same fixed one (else 0), ``discarded`` the records of weight 0."""
+
+    def __init__(self, ctx, paths: Sequence[str], slices: Optional[Sequence[Optional[slice]]] = None, *,
+                 threshold: float = 1.0, table=None, chunk_records: Optional[int] = None,
+                 block_bytes: Optional[int] = None, want_means: bool = False):
+        import os
+        self.ctx, self.paths, self.slices = ctx, list(paths), (list(slices) if slices else None)
+        self.threshold, self.table, self.want_means = float(threshold), table, want_means
+        self.chunk_records = int(chunk_records or os.environ.get("FQD_FASTQ_CHUNK_RECORDS", 2_000_000))
+        self.block_bytes = int(block_bytes or os.environ.get("FQD_FASTQ_BLOCK_BYTES", 64 << 20))
+        self.n = self.key_bytes = self.discarded = 0
+        self.key_len = 0
+        self.keys = self.offsets = self.weights = self.means = None
+
+    def _key_bound(self, f: int, max_record: int) -> int:
+        """Most key bytes one record of file f can give: half the record (sequence and quality are equally
+        long), less when the slice says so on its face."""
+        bound = max_record // 2
+        sl = self.slices[f] if self.slices else None
+        if sl is not None and sl.stop is not None and sl.stop >= 0 and (sl.step or 1) > 0 and (sl.start or 0) >= 0:
+            bound = min(bound, max(0, -(-(sl.stop - (sl.start or 0)) // (sl.step or 1))))
+        return bound
+
+    @staticmethod
+    def _grown(t, used: int, need: int):
+        if need <= t.numel():
+            return t
+        import torch
+        bigger = torch.empty(max(need, 2 * t.numel()), dtype=t.dtype, device=t.device)
+        bigger[:used] = t[:used]
+        return bigger
+
+    def run(self) -> "DeviceIngest":
+        import torch
+        from ._lib import FASTQ_ERRORS
+        ctx, nf = self.ctx, len(self.paths)
+        dev = torch.device("cuda", ctx.device)
+        gate = self.threshold < 1.0
+        self.keys = torch.empty(1 << 20, dtype=torch.uint8, device=dev)
+        self.offsets = torch.zeros(1 << 16, dtype=torch.int64, device=dev)
+        self.weights = torch.empty(1 << 16, dtype=torch.int32, device=dev) if gate else None
+        self.means = torch.empty(1 << 16, dtype=torch.float64, device=dev) if self.want_means else None
+        ctx.fastq_begin(nf)
+        handles, fixed = [], None
+        try:
+            for p in self.paths:
+                handles.append(_open_read(p))
+            blocks = [_HostBlock(self.block_bytes) for _ in handles]
+            while True:
+                infos = []
+                for f, b in enumerate(blocks):
+                    if not b.eof:
+                        b.read(handles[f], self.block_bytes - b.fill if b.fill < self.block_bytes else self.block_bytes)
+                    info = ctx.fastq_index(f, b.t, b.fill, final=b.eof, first_line=4 * self.n)
+                    if info.error_kind:
+                        raise FastqFormatError(FASTQ_ERRORS[info.error_kind], line=int(info.error_line))
+                    infos.append(info)
+                n = min(min(int(i.n_records) for i in infos), self.chunk_records)
+                if n:
+                    room = min(sum(b.fill for b in blocks) // 2,
+                               n * sum(self._key_bound(f, int(i.max_record_bytes)) for f, i in enumerate(infos)))
+                    self.keys = self._grown(self.keys, self.key_bytes, self.key_bytes + room + 16)
+                    self.offsets = self._grown(self.offsets, self.n + 1, self.n + n + 1)
+                    if gate:
+                        self.weights = self._grown(self.weights, self.n, self.n + n)
+                    if self.want_means:
+                        self.means = self._grown(self.means, self.n, self.n + n)
+                    out = ctx.fastq_append(n, self.keys, self.key_bytes, self.offsets[self.n:],
+                                           self.weights[self.n:] if gate else None,
+                                           self.means[self.n:] if self.want_means else None, slices=self.slices,
+                                           threshold=self.threshold, table=self.table)
+                    if out.first_non_mate != 0xFFFFFFFFFFFFFFFF:
+                        names = ", ".join(bytes(b.a[out.name_start[f]:out.name_start[f] + out.name_len[f]])
+                                          .decode("ascii", "replace") for f, b in enumerate(blocks))
+                        raise FastqFormatError(f"FASTQ files not in sync: {names} are not mates.", line=None)
+                    fixed = out.fixed_len if fixed is None else (fixed if fixed == out.fixed_len else 0)
+                    self.key_bytes += int(out.key_bytes)
+                    self.discarded += int(out.n_discarded)
+                    self.n += n
+                    for f, b in enumerate(blocks):
+                        b.drop(int(out.consumed[f]))
+                if any(b.eof and int(infos[f].n_records) == n for f, b in enumerate(blocks)):
+                    break           # some file has ended: a tuple needs a record of every file
+        finally:
+            for fh in handles:
+                fh.close()
+        self.key_len = int(fixed or 0)
+        return self
+
+
+# ---------------------------------------------------------------------------
 # pass 2
 # ---------------------------------------------------------------------------
 

@@ -426,6 +426,63 @@ int fqd_quality_filter(fqd_ctx *ctx, const uint8_t *bytes, const uint64_t *offse
                        const double *table128, uint32_t *pass_out, double *means_out,
                        uint64_t *n_discarded, int mem);
 
+/* ---- FASTQ ingest: raw file bytes to keys, offsets and weights on the device ----
+ * Replaces the host passes in front of fqd_cluster_keys: the reference's record loop and zip over its
+ * readers (__init__.py:54-57, :180), the mate check (:181-185), the --check-lengths slices of sequence
+ * and qualities (:160-167) and the quality gate as pass 1 applies it (:243-251). The host finds no
+ * newline, span or slice: it hands over one block of decompressed bytes per input file, learns how many
+ * complete records each block holds, and appends the first n records of every block to its own device
+ * buffers. Blocks are shorter than 4 GiB and there are at most FQD_FASTQ_MAX_FILES files. */
+#define FQD_FASTQ_MAX_FILES 8
+#define FQD_FASTQ_OK          0
+#define FQD_FASTQ_NO_AT       1   /* "Line expected to start with '@'" */
+#define FQD_FASTQ_NO_PLUS     2   /* "Line expected to start with '+'" */
+#define FQD_FASTQ_LENGTHS     3   /* "Length of sequence and qualities differ" */
+#define FQD_FASTQ_PREMATURE   4   /* "Premature end of file encountered." (final blocks only) */
+typedef struct {
+    uint64_t n_records;          /* complete records in the block */
+    uint64_t error_line;         /* line of the first fault, counted from first_line */
+    uint32_t max_record_bytes;   /* the largest record, line ends included */
+    int32_t error_kind;          /* FQD_FASTQ_* */
+} fqd_fastq_index_info;
+/* A Python slice; None as CPython passes it to PySlice_AdjustIndices: start 0 and stop INT64_MAX for a positive
+ * step, start INT64_MAX and stop INT64_MIN for a negative one. step != 0. */
+typedef struct {
+    int64_t start, stop, step;
+} fqd_fastq_slice;
+typedef struct {
+    uint64_t key_bytes;                           /* written behind key_base */
+    uint64_t n_discarded;                         /* records with weight 0 */
+    uint64_t first_non_mate;                      /* first record whose ids differ between the files, or ~0 */
+    uint64_t consumed[FQD_FASTQ_MAX_FILES];       /* bytes of each block the n records took: the end of record n - 1 */
+    uint64_t name_start[FQD_FASTQ_MAX_FILES];     /* of record first_non_mate in each block (for the message) */
+    uint32_t name_len[FQD_FASTQ_MAX_FILES];
+    uint32_t fixed_len;                           /* the key length when all n keys are equally long, else 0 */
+    uint32_t reserved;
+} fqd_fastq_append_info;
+/* Forget the blocks of all files and zero the counters of fqd_fastq_stats. */
+int fqd_fastq_begin(fqd_ctx *ctx, uint32_t n_files);
+/* Index one block of file `file` (replaces __init__.py:54-57): host bytes are copied into a buffer of the
+ * context, device bytes (16-byte aligned) are read in place and must stay until the appends from them are done.
+ * The block starts at a record's first byte; `final` says that the file ends with it (a last line without a
+ * newline then counts, trailing blank lines do not). first_line: the file's line number of the block's first line. */
+int fqd_fastq_index(fqd_ctx *ctx, uint32_t file, const uint8_t *bytes, uint64_t n_bytes, int mem, int final,
+                    uint64_t first_line, fqd_fastq_index_info *info);
+/* The first n records of every indexed block (replaces __init__.py:160-167, :180-185, :243-251): key i is the
+ * concatenation over the files of sequence[slice]; its bytes go to keys_out[key_base ..), offsets_out gets n + 1
+ * entries starting with key_base, weights_out[i] = !(mean error rate of the equally sliced and joined quality
+ * strings > threshold), bit-identical to fqd_quality_filter. All *_out are DEVICE buffers of the caller
+ * (keys_out 16-byte aligned, keys_capacity bytes long); means_out may be NULL; with threshold >= 1.0 no weights
+ * are written and no phred byte is looked at unless means_out is given. slices: one per file, or NULL for whole
+ * sequences. table128 as in fqd_quality_filter. FQD_E_VALUE when the keys do not fit keys_capacity or a phred
+ * byte is out of range. When the files are not mates (info->first_non_mate != ~0) the call returns FQD_OK and what
+ * it wrote to the *_out buffers is to be discarded. */
+int fqd_fastq_append(fqd_ctx *ctx, uint64_t n, const fqd_fastq_slice *slices, double threshold, const double *table128,
+                     uint32_t phred_offset, uint8_t *keys_out, uint64_t keys_capacity, uint64_t key_base,
+                     uint64_t *offsets_out, uint32_t *weights_out, double *means_out, fqd_fastq_append_info *info);
+/* Since fqd_fastq_begin: records appended, key bytes written, records discarded, appends. */
+int fqd_fastq_stats(fqd_ctx *ctx, uint64_t *out4);
+
 /* ---- measurement ----------------------------------------------------------- */
 #define FQD_T_PACK       0
 #define FQD_T_COLLAPSE   1
@@ -460,7 +517,13 @@ int fqd_stage_times(fqd_ctx *ctx, float *ms /* FQD_T_COUNT */, uint32_t *launche
 #define FQD_K_KEPT_FLAGS    17   /* verdict per unique key + the byte map of kept first-holder ids */
 #define FQD_K_PART_SCATTER12 18  /* level 2 and the dedupe of the compact (12-byte) records of fqd_cluster_keys */
 #define FQD_K_DEDUPE12      19
-#define FQD_K_COUNT         20
+#define FQD_K_FASTQ_LINE_COUNT   20   /* the FASTQ ingest: newline count per tile, */
+#define FQD_K_FASTQ_LINE_SCATTER 21   /* newline positions, */
+#define FQD_K_FASTQ_RECORDS      22   /* record spans and format checks, */
+#define FQD_K_FASTQ_MATES        23   /* id comparison between the files, */
+#define FQD_K_FASTQ_KEY_LENS     24   /* sliced key lengths, */
+#define FQD_K_FASTQ_GATHER       25   /* key bytes + quality gate */
+#define FQD_K_COUNT         26
 int fqd_kernel_times(fqd_ctx *ctx, float *ms /* FQD_K_COUNT */, uint32_t *launches /* FQD_K_COUNT */,
                      int reset);
 /* What is timed. Timers never synchronise the host: they are event pairs recorded while the work
