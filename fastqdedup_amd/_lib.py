@@ -40,6 +40,7 @@ FASTQ_MAX_FILES = 8
 FASTQ_LINE_TILE = 4096          # bytes per workgroup of the line index (fastq_ingest.hip FQ_LINE_TILE)
 FASTQ_SCAN_STEP = 1024 * 16     # tile counts one step of the one-workgroup scan takes (prims.hip SS_THREADS * SS_PER)
 FASTQ_IN_TILE = 32 * 1024       # LDS input tile of the gather kernel (fastq_ingest.hip FQ_IN_TILE)
+FASTQ_EMIT_TILE = 16 * 1024     # output bytes per workgroup of the emit's copy kernel (fastq_emit.hip FQ_EMIT_TILE)
 FASTQ_ERRORS = {1: "Line expected to start with '@'", 2: "Line expected to start with '+'",
                 3: "Length of sequence and qualities differ", 4: "Premature end of file encountered."}
 
@@ -59,6 +60,11 @@ class FastqAppendInfo(C.Structure):
                 ("name_len", C.c_uint32 * FASTQ_MAX_FILES), ("fixed_len", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FastqEmitInfo(C.Structure):
+    _fields_ = [("n_emitted", C.c_uint64), ("out_bytes", C.c_uint64 * FASTQ_MAX_FILES),
+                ("consumed", C.c_uint64 * FASTQ_MAX_FILES)]
+
+
 # every symbol include/fqdedup_hip.h declares (tests check the library exports them all)
 EXPORTS = [
     "fqd_device_count", "fqd_global_error", "fqd_create", "fqd_destroy", "fqd_last_error",
@@ -73,6 +79,7 @@ EXPORTS = [
     "fqd_trie_order", "fqd_trie_stats", "fqd_store_symbol_events", "fqd_get_stream", "fqd_pack_collapse", "fqd_synth_indel_keys", "fqd_copy_bandwidth",
     "fqd_synth_keys_skewed", "fqd_get_route", "fqd_cluster_subgraph", "fqd_cluster_subgraph_home", "fqd_dissect_except",
     "fqd_fastq_begin", "fqd_fastq_index", "fqd_fastq_append", "fqd_fastq_stats",
+    "fqd_fastq_emit_begin", "fqd_fastq_emit",
     "fqd_owner_routing_possible", "fqd_set_owner_routing", "fqd_dense_owner_slabs", "fqd_owner_slab_geometry", "fqd_pack_to_owner_slabs", "fqd_collapse_owner_slabs",
 ]
 
@@ -193,6 +200,8 @@ def load() -> C.CDLL:
     L.fqd_fastq_append.argtypes = [vp, C.c_uint64, vp, C.c_double, vp, C.c_uint32, vp, C.c_uint64, C.c_uint64, vp, vp, vp,
                                    C.POINTER(FastqAppendInfo)]
     L.fqd_fastq_stats.argtypes = [vp, u64p]
+    L.fqd_fastq_emit_begin.argtypes = [vp, C.c_uint32]
+    L.fqd_fastq_emit.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint64, vp, vp, C.POINTER(FastqEmitInfo)]
     L.fqd_stage_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     L.fqd_kernel_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]
     L.fqd_set_timing.argtypes = [vp, C.c_int, C.c_uint32]
@@ -789,6 +798,27 @@ class Context:
         self._ck(self._L.fqd_fastq_stats(self._h, v))
         return {"records": int(v[0]), "key_bytes": int(v[1]), "discarded": int(v[2]), "chunks": int(v[3])}
 
+    # ---- FASTQ emit --------------------------------------------------------------
+    def fastq_emit_begin(self, n_files: int) -> None:
+        """The block slots of ``n_files`` files for pass 2; ``fastq_stats`` keeps what pass 1 counted."""
+        self._ck(self._L.fqd_fastq_emit_begin(self._h, int(n_files)))
+
+    def fastq_emit(self, n: int, base_id: int, kept_ids, n_kept: int, kept_from: int, outs) -> FastqEmitInfo:
+        """The kept records among the first n of every indexed block, as ``@name\\nseq\\n+\\nqual\\n``, into the front
+        of one device uint8 tensor per file (fqd_fastq_emit). ``kept_ids``: ascending record numbers on the device
+        (8-byte integers), ``kept_from`` of them passed by earlier chunks; the first record here is ``base_id``."""
+        for t in (kept_ids, *outs):
+            if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous()):
+                raise ValueError("fastq_emit reads and writes contiguous device tensors")
+        if kept_ids.element_size() != 8 or n_kept > kept_ids.numel():
+            raise ValueError("kept_ids: n_kept 8-byte integers")
+        ptrs = (C.c_void_p * FASTQ_MAX_FILES)(*[t.data_ptr() for t in outs])
+        caps = (C.c_uint64 * FASTQ_MAX_FILES)(*[t.numel() * t.element_size() for t in outs])
+        info = FastqEmitInfo()
+        self._ck(self._L.fqd_fastq_emit(self._h, int(n), int(base_id), kept_ids.data_ptr(), int(n_kept), int(kept_from),
+                                        ptrs, caps, C.byref(info)))
+        return info
+
     # ---- the Trie object as a device-resident store ------------------------------
     @staticmethod
     def _alphabet_bytes(alphabet: str) -> np.ndarray:
@@ -880,7 +910,8 @@ class Context:
                "write_unique_kernel", "segment_hashes_kernel", "bucket_pairs_kernel", "uf_union_kernel",
                "uf_flatten_kernel", "dissect_round_kernel", "gp_hist_kernel", "gp_scatter_kernel", "verify_candidates_kernel", "kept_flags_kernel",
                "part_scatter12_kernel", "bucket_dedupe12_kernel", "fastq_line_count_kernel", "fastq_line_scatter_kernel",
-               "fastq_records_kernel", "fastq_mates_kernel", "fastq_key_lens_kernel", "fastq_gather_kernel"]
+               "fastq_records_kernel", "fastq_mates_kernel", "fastq_key_lens_kernel", "fastq_gather_kernel",
+               "fastq_emit_sizes_kernel", "fastq_emit_copy_kernel"]
 
     def kernel_times(self, reset: bool = True):
         """{kernel: (ms summed over launches, launches)} since the last reset."""

@@ -24,6 +24,7 @@ from .core import (CLUSTER_DISSECTION_METHODS, DEFAULT_MAX_DISTANCE, TableCensus
 DEFAULT_PREFIX = "fastqdedup_R"
 DEFAULT_CLUSTER_DISSECTION = "directional"
 DEFAULT_MAX_AVERAGE_ERROR_RATE = 0.001
+DEFAULT_EMIT = "device"         # route of pass 2 without FQD_EMIT in the environment
 
 ClusterDissectionFunc = Callable[[List[Tuple[int, str]], int, bool], Iterator[str]]
 
@@ -223,15 +224,20 @@ def deduplicate_cluster(input_files: List[str], output_files: List[str], check_s
                 f"({timer.get_difference()})")
 
     # ---- pass 2 (reference :189-206): the files are streamed again; the records whose numbers the
-    # GPU returned are written (the first holder of every kept key, filtered or not)
+    # GPU returned are written (the first holder of every kept key, filtered or not). Two routes to the same bytes:
+    # the device emit (fastq.DeviceEmit: the host reads blocks and writes what the device compacted; default) and,
+    # with FQD_EMIT=host, the numpy pass
     keep = res.kept_read_ids.astype(np.int64) if res else np.zeros(0, dtype=np.int64)
     outs = [fastq.open_write(path) for path in output_files]
     try:
-        for tables, m, first in fastq.zip_chunks(input_files, chunk_records):
-            lo, hi = np.searchsorted(keep, [first, first + m])
-            local = keep[lo:hi] - first
-            for table, out in zip(tables, outs):
-                fastq.write_records_to(table, local, out)
+        if os.environ.get("FQD_EMIT", DEFAULT_EMIT) != "host":
+            fastq.DeviceEmit(ctx, input_files, outs, keep, chunk_records=chunk_records).run()
+        else:
+            for tables, m, first in fastq.zip_chunks(input_files, chunk_records):
+                lo, hi = np.searchsorted(keep, [first, first + m])
+                local = keep[lo:hi] - first
+                for table, out in zip(tables, outs):
+                    fastq.write_records_to(table, local, out)
     finally:
         for out in outs:
             out.close()

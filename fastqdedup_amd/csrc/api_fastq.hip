@@ -1,7 +1,8 @@
 // api_fastq.hip -- the FASTQ ingest behind the C ABI (include/fqdedup_hip.h, fqd_fastq_*): one block of raw
 // bytes per input file is indexed on the device (fastq_ingest.hip kernels 1-2), then the first n records of
 // every block are turned into key bytes, offsets and weights in the caller's device buffers (kernels 3-5).
-// One read-back per index call and one per append.
+// One read-back per index call and one per append. Pass 2 (fqd_fastq_emit*) indexes the blocks the same way and turns
+// the kept records among the first n into every file's output bytes (fastq_emit.hip): one read-back per emit.
 #include "api_ctx.h"
 
 namespace {
@@ -225,6 +226,91 @@ int fqd_fastq_append(fqd_ctx *c, uint64_t n, const fqd_fastq_slice *slices, doub
     c->fq_records += n;
     c->fq_key_bytes += info->key_bytes;
     c->fq_discarded += info->n_discarded;
+    return FQD_OK;
+}
+
+int fqd_fastq_emit_begin(fqd_ctx *c, uint32_t n_files)
+{
+    FQD_TRY(bind(c));
+    if (!n_files || n_files > FQD_FASTQ_MAX_FILES)
+        return fail(c, FQD_E_VALUE, "fqd_fastq_emit_begin: between 1 and FQD_FASTQ_MAX_FILES files");
+    c->fq_files = n_files;
+    for (FastqSlot &s : c->fq) {
+        s.indexed = s.faulty = false;
+        s.n_rec = s.n_bytes = 0;
+        s.d = nullptr;
+    }
+    return FQD_OK;          // (the counters of fqd_fastq_stats belong to pass 1)
+}
+
+int fqd_fastq_emit(fqd_ctx *c, uint64_t n, uint64_t base_id, const uint64_t *kept_ids, uint64_t n_kept, uint64_t kept_from,
+                   uint8_t *const *out, const uint64_t *out_capacity, fqd_fastq_emit_info *info)
+{
+    FQD_TRY(bind(c));
+    if (!info || !out || !out_capacity || (n_kept && !kept_ids))
+        return fail(c, FQD_E_VALUE, "fqd_fastq_emit: null argument");
+    if (kept_from > n_kept)
+        return fail(c, FQD_E_VALUE, "fqd_fastq_emit: kept_from lies behind the kept ids");
+    if (!c->fq_files)
+        return fail(c, FQD_E_STATE, "fqd_fastq_emit before fqd_fastq_emit_begin");
+    memset(info, 0, sizeof *info);
+    uint64_t block_bytes = 0;
+    for (uint32_t f = 0; f < c->fq_files; f++) {
+        const FastqSlot &s = c->fq[f];
+        if (!s.indexed || s.faulty)
+            return fail(c, FQD_E_STATE, "fqd_fastq_emit: every file needs a block indexed without a format error");
+        if (n > s.n_rec)
+            return fail(c, FQD_E_VALUE, "fqd_fastq_emit: more records than a block holds");
+        if (((uintptr_t)out[f] & 15u) || (!out[f] && out_capacity[f]))
+            return fail(c, FQD_E_VALUE, "device buffer must be 16-byte aligned");
+        block_bytes += s.n_bytes;
+    }
+    if (block_bytes >= 0xFFFFFFF0ull)
+        return fail(c, FQD_E_VALUE, "fqd_fastq_emit: the blocks of all files together must be shorter than 4 GiB");
+    if (!n)
+        return FQD_OK;
+    const uint32_t m = (uint32_t)std::min<uint64_t>(n, n_kept - kept_from);
+    if (!m) {
+        // nothing left to write: only where the chunk ends in every block
+        for (uint32_t f = 0; f < c->fq_files; f++) {
+            const FastqSlot &s = c->fq[f];
+            uint32_t end = 0;
+            FQD_TRY(read_words(c, &end, s.spans.as<uint32_t>() + (size_t)fqd::FQS_REC_END * s.rec_cap + (n - 1), 4));
+            info->consumed[f] = end;
+        }
+        return FQD_OK;
+    }
+    const uint64_t *kept = kept_ids + kept_from;
+    HIP_TRY(c, c->fq_ctr.reserve(std::max<size_t>(fqd::FQC_WORDS, fqd::FQE_WORDS) * 4));
+    HIP_TRY(c, c->fq_lens.reserve((size_t)m * 4 + 16));
+    HIP_TRY(c, c->fq_incl.reserve((size_t)m * 4 + 16));
+    uint32_t *ctr = c->fq_ctr.as<uint32_t>(), *sizes = c->fq_lens.as<uint32_t>(), *incl = c->fq_incl.as<uint32_t>();
+    HIP_TRY(c, fqd::launch_fastq_emit_init(ctr, c->st));
+    for (uint32_t f = 0; f < c->fq_files; f++) {
+        const FastqSlot &s = c->fq[f];
+        const uint32_t *spans = s.spans.as<uint32_t>();
+        KTIME(c, FQD_K_FASTQ_EMIT_SIZES,
+              fqd::launch_fastq_emit_sizes(spans, s.rec_cap, f, (uint32_t)n, base_id, kept, m, sizes, ctr, c->st));
+        FQD_TRY(scan_u32(c, sizes, incl, m));
+        // the grid: a record's output is its raw bytes or less, but for one newline the last record may lack
+        KTIME(c, FQD_K_FASTQ_EMIT_COPY,
+              fqd::launch_fastq_emit_copy(s.d, spans, s.rec_cap, f, (uint32_t)n, base_id, kept, m, incl, s.n_bytes + 1,
+                                          out[f], out_capacity[f], ctr, c->st));
+    }
+    uint32_t words[fqd::FQE_WORDS];
+    FQD_TRY(read_words(c, words, ctr, sizeof words));
+    if (c->kused > fqd_ctx::KPOOL - 40)
+        ktime_collect(c);
+    if (words[fqd::FQE_FAULT])
+        return fail(c, FQD_E_VALUE, "fqd_fastq_emit: a kept id at kept_from lies below base_id (ids ascending, cursor past "
+                                    "the earlier chunks?)");
+    if (words[fqd::FQE_OVERFLOW])
+        return fail(c, FQD_E_VALUE, "fqd_fastq_emit: out_capacity is too small for the kept records of this chunk");
+    info->n_emitted = words[fqd::FQE_TAKEN];
+    for (uint32_t f = 0; f < c->fq_files; f++) {
+        info->out_bytes[f] = words[fqd::FQE_BYTES + f];
+        info->consumed[f] = words[fqd::FQE_CONSUMED + f];
+    }
     return FQD_OK;
 }
 

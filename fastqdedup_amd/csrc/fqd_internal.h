@@ -853,4 +853,21 @@ hipError_t launch_fastq_gather(const FastqFiles &files, uint32_t n, uint32_t R, 
                                uint8_t *keys_out, uint64_t keys_capacity, uint64_t key_base, uint64_t *offsets_out,
                                uint32_t *weights_out, double *means_out, uint32_t *ctr, hipStream_t st);
 
+// fastq_emit.hip -- the kept records of a chunk as output bytes, file by file
+// bytes of a file's output one workgroup of the copy kernel assembles in LDS. 16 KiB and a few words of state: eight
+// workgroups of four waves fit a CU's 160 KiB, which is all the waves a CU takes -- the kernel waits on scattered
+// reads of the block, so it wants waves in flight rather than a longer tile (32 KiB would halve them)
+constexpr uint32_t FQ_EMIT_TILE = 16 * 1024;
+// the 32-bit words of one emit (read back in one copy)
+enum FastqEmitCounter { FQE_FAULT = 0, FQE_OVERFLOW, FQE_TAKEN, FQE_PAD, FQE_BYTES, FQE_CONSUMED = FQE_BYTES + FQ_MAX_FILES,
+                        FQE_WORDS = FQE_CONSUMED + FQ_MAX_FILES };
+hipError_t launch_fastq_emit_init(uint32_t *ctr, hipStream_t st);
+// kept: the first of the m candidate ids (the caller's list from its cursor on); sizes[m]
+hipError_t launch_fastq_emit_sizes(const uint32_t *spans, uint32_t rec_cap, uint32_t file, uint32_t n, uint64_t base,
+                                   const uint64_t *kept, uint32_t m, uint32_t *sizes, uint32_t *ctr, hipStream_t st);
+// incl: the inclusive scan of sizes; bound: no fewer bytes than incl[m - 1] (the grid is sized from it)
+hipError_t launch_fastq_emit_copy(const uint8_t *bytes, const uint32_t *spans, uint32_t rec_cap, uint32_t file, uint32_t n,
+                                  uint64_t base, const uint64_t *kept, uint32_t m, const uint32_t *incl, uint64_t bound,
+                                  uint8_t *out, uint64_t out_capacity, uint32_t *ctr, hipStream_t st);
+
 }  // namespace fqd

@@ -11,7 +11,8 @@ Reproduced behaviour (reference file:line):
   * ``--check-lengths`` slices use Python slice semantics on the sequence AND on the
     quality string of each file (:160-167, :243-251);
   * pass 2 writes ``@name\\nseq\\n+\\nqual\\n`` (dnaio ``fastq_bytes``), gzip level 1 for
-    ``.gz`` names (:197-198).
+    ``.gz`` names (:197-198) -- composed on the device by ``DeviceEmit``, or on the host by
+    ``write_records_to``.
 """
 from __future__ import annotations
 
@@ -471,6 +472,78 @@ def write_records_to(table: FastqTable, keep: np.ndarray, out) -> None:
         out.write(b"@" + b[table.name_start[i]:table.name_end[i]].tobytes() + b"\n" +
                   b[table.seq_start[i]:table.seq_end[i]].tobytes() + b"\n+\n" +
                   b[table.qual_start[i]:table.qual_end[i]].tobytes() + b"\n")
+
+
+class DeviceEmit:
+    """Pass 2 of ``deduplicate_cluster`` with the record selection on the device: what ``zip_chunks`` +
+    ``write_records_to`` do on the host (reference __init__.py:189-206). The block loop is ``DeviceIngest``'s: the
+    host reads a block of every file, the device indexes it (``Context.fastq_index``) and writes the kept records among
+    those every file has complete into one output tensor per file (``Context.fastq_emit``); these bytes come back
+    through a page-locked buffer and go to ``out_handles[f].write``. ``kept_ids``: the ascending record numbers to
+    keep, a numpy array (uploaded once) or a device tensor of 8-byte integers; ids at or beyond the shortest file's
+    record count are never written. After ``run()``: ``n`` records seen, ``n_emitted`` records written per file."""
+
+    def __init__(self, ctx, paths: Sequence[str], out_handles, kept_ids, *, chunk_records: Optional[int] = None,
+                 block_bytes: Optional[int] = None):
+        import os
+        self.ctx, self.paths, self.outs, self.kept_ids = ctx, list(paths), list(out_handles), kept_ids
+        if len(self.paths) != len(self.outs):
+            raise ValueError("one output handle per input file")
+        self.chunk_records = int(chunk_records or os.environ.get("FQD_FASTQ_CHUNK_RECORDS", 2_000_000))
+        self.block_bytes = int(block_bytes or os.environ.get("FQD_FASTQ_BLOCK_BYTES", 64 << 20))
+        self.n = self.n_emitted = 0
+
+    def run(self) -> "DeviceEmit":
+        import torch
+        from ._lib import FASTQ_ERRORS
+        ctx, nf = self.ctx, len(self.paths)
+        dev = torch.device("cuda", ctx.device)
+        kept = self.kept_ids
+        if not hasattr(kept, "is_cuda"):
+            kept = torch.from_numpy(np.ascontiguousarray(kept, dtype=np.uint64).view(np.int64)).to(dev)
+        n_kept = kept.numel()
+        d_out = [torch.empty(16, dtype=torch.uint8, device=dev) for _ in range(nf)]
+        h_out = [torch.empty(16, dtype=torch.uint8, pin_memory=True) for _ in range(nf)]
+        ctx.fastq_emit_begin(nf)
+        handles = []
+        try:
+            for p in self.paths:
+                handles.append(_open_read(p))
+            blocks = [_HostBlock(self.block_bytes) for _ in handles]
+            while True:
+                infos = []
+                for f, b in enumerate(blocks):
+                    if not b.eof:
+                        b.read(handles[f], self.block_bytes - b.fill if b.fill < self.block_bytes else self.block_bytes)
+                    info = ctx.fastq_index(f, b.t, b.fill, final=b.eof, first_line=4 * self.n)
+                    if info.error_kind:
+                        raise FastqFormatError(FASTQ_ERRORS[info.error_kind], line=int(info.error_line))
+                    infos.append(info)
+                n = min(min(int(i.n_records) for i in infos), self.chunk_records)
+                if n:
+                    for f, b in enumerate(blocks):
+                        if d_out[f].numel() < b.fill + 16:       # (what a block's records give is no longer than the block + 1)
+                            d_out[f] = torch.empty(b.fill + 16, dtype=torch.uint8, device=dev)
+                            h_out[f] = torch.empty(b.fill + 16, dtype=torch.uint8, pin_memory=True)
+                    out = ctx.fastq_emit(n, self.n, kept, n_kept, self.n_emitted, d_out)
+                    sizes = [int(out.out_bytes[f]) for f in range(nf)]
+                    for f, nb in enumerate(sizes):
+                        if nb:
+                            h_out[f][:nb].copy_(d_out[f][:nb], non_blocking=True)
+                    torch.cuda.current_stream(dev).synchronize()
+                    for f, nb in enumerate(sizes):
+                        if nb:
+                            self.outs[f].write(memoryview(h_out[f].numpy())[:nb])
+                    self.n_emitted += int(out.n_emitted)
+                    self.n += n
+                    for f, b in enumerate(blocks):
+                        b.drop(int(out.consumed[f]))
+                if any(b.eof and int(infos[f].n_records) == n for f, b in enumerate(blocks)):
+                    break           # some file has ended: a tuple needs a record of every file
+        finally:
+            for fh in handles:
+                fh.close()
+        return self
 
 
 def write_records(table: FastqTable, keep: np.ndarray, path: str) -> None:

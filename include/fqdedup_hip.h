@@ -483,6 +483,33 @@ int fqd_fastq_append(fqd_ctx *ctx, uint64_t n, const fqd_fastq_slice *slices, do
 /* Since fqd_fastq_begin: records appended, key bytes written, records discarded, appends. */
 int fqd_fastq_stats(fqd_ctx *ctx, uint64_t *out4);
 
+/* ---- FASTQ emit: the kept records of a chunk as output bytes on the device ----
+ * Replaces the host's second pass over the files, the write loop over the records that
+ * filter_fastq_files_on_set selects (__init__.py:189-206): the blocks are indexed again with fqd_fastq_index, and
+ * for every kept record of the chunk, in order, each file's output buffer receives exactly
+ *     '@' name '\n' sequence '\n' '+' '\n' quality '\n'
+ * -- dnaio's fastq_bytes: the name to the end of its line without a '\r', the '+' line bare, a final newline also
+ * where the input lacks it. For input already in that form these are the raw bytes of the kept records. */
+typedef struct {
+    uint64_t n_emitted;                           /* kept ids this chunk took: the cursor moves on by this */
+    uint64_t out_bytes[FQD_FASTQ_MAX_FILES];      /* written to the front of each file's output buffer */
+    uint64_t consumed[FQD_FASTQ_MAX_FILES];       /* bytes of each block the n records took: the end of record n - 1 */
+} fqd_fastq_emit_info;
+/* Make the block slots of n_files files ready for fqd_fastq_index and forget what they held -- pass 2 of
+ * __init__.py:189-206 opens the files anew. The counters of fqd_fastq_stats are pass 1's and stay as they are. */
+int fqd_fastq_emit_begin(fqd_ctx *ctx, uint32_t n_files);
+/* The first n records of every indexed block are records base_id .. base_id + n of the run (__init__.py:189-206
+ * numbers them as it reads). kept_ids: n_kept ascending, distinct record numbers in DEVICE memory, of which
+ * kept_from have been passed by earlier chunks, so kept_ids[kept_from] >= base_id (else FQD_E_VALUE). The kept
+ * records among the n go to out[f][0 ..) for every file f: DEVICE buffers of the caller, 16-byte aligned,
+ * out_capacity[f] bytes long; the records of one block never need more than the block's bytes + 1. When an output
+ * does not fit, FQD_E_VALUE is returned and nothing is written to any byte at or behind the capacity. With n == 0
+ * or no kept id left nothing is launched and nothing written; consumed is reported whenever n > 0. Faulty or
+ * unindexed blocks and blocks of 4 GiB together are refused as by fqd_fastq_append. */
+int fqd_fastq_emit(fqd_ctx *ctx, uint64_t n, uint64_t base_id, const uint64_t *kept_ids, uint64_t n_kept,
+                   uint64_t kept_from, uint8_t *const out[FQD_FASTQ_MAX_FILES],
+                   const uint64_t out_capacity[FQD_FASTQ_MAX_FILES], fqd_fastq_emit_info *info);
+
 /* ---- measurement ----------------------------------------------------------- */
 #define FQD_T_PACK       0
 #define FQD_T_COLLAPSE   1
@@ -523,7 +550,9 @@ int fqd_stage_times(fqd_ctx *ctx, float *ms /* FQD_T_COUNT */, uint32_t *launche
 #define FQD_K_FASTQ_MATES        23   /* id comparison between the files, */
 #define FQD_K_FASTQ_KEY_LENS     24   /* sliced key lengths, */
 #define FQD_K_FASTQ_GATHER       25   /* key bytes + quality gate */
-#define FQD_K_COUNT         26
+#define FQD_K_FASTQ_EMIT_SIZES   26   /* the FASTQ emit: output size of every kept record of a chunk, */
+#define FQD_K_FASTQ_EMIT_COPY    27   /* the output bytes, a tile per workgroup */
+#define FQD_K_COUNT         28
 int fqd_kernel_times(fqd_ctx *ctx, float *ms /* FQD_K_COUNT */, uint32_t *launches /* FQD_K_COUNT */,
                      int reset);
 /* What is timed. Timers never synchronise the host: they are event pairs recorded while the work
