@@ -136,6 +136,7 @@ struct fqd_ctx {
     bool gp_fine_ok = false;       // the last grouped pass: its crowded keys can be matched on finer pieces
     bool gp_fine_used = false;     // the last grouped_refine filed fine items (its candidates count towards the budget)
     bool gp_tiles = false;         // grouped search: crowded buckets go all pairs in tiles (the finer pieces did not split them)
+    bool gp_inplace = false;       // grouped search: one-uint4 records are verified in the buckets' LDS (the candidate lists outgrew their budget once)
     bool gp_slab_off = false;      // grouped search: same, for the (hash, uid) partition
     bool slab_off = false;         // LDS collapse: a slab of level 2 overflowed once, use exact bucket sizes
     bool hashes_valid = false;     // `hashes` holds the record hashes of the packed reads (lazy after an import)

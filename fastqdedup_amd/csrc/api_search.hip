@@ -477,8 +477,9 @@ static CrowdedBuf crowded_buf(fqd_ctx *c, uint32_t n_buckets)
     return b;
 }
 
+// inplace: records of one uint4 -- the buckets' pairs are verified where they are found (group_inplace.hip), no list
 static int grouped_pass(fqd_ctx *c, const uint32_t *hashes, uint64_t U, uint32_t d, uint32_t s, uint32_t nseg,
-                        uint32_t fused_U = 0)
+                        uint32_t fused_U = 0, bool inplace = false)
 {
     const KeyShape sh = c->ks;
     uint32_t B = 8;
@@ -532,6 +533,13 @@ static int grouped_pass(fqd_ctx *c, const uint32_t *hashes, uint64_t U, uint32_t
         skip = flags;
         c->gp_crowded_bits = B;
     }
+    if (inplace) {
+        KTIME(c, FQD_K_PAIRS, fqd::launch_grouped_inplace(items, c->ld_start.as<uint32_t>(), bucket_end, n_buckets, B, skip,
+                                                          0, nullptr, c->urecs.as<uint32_t>(), c->ulens.as<uint32_t>(),
+                                                          c->ks, d, s, nseg, c->edges.as<uint32_t>(), ctr + C64_EDGES,
+                                                          c->edge_cap, c->d_stats.as<fqd::PairStats>(), c->st, fused_U));
+        return FQD_OK;
+    }
     KTIME(c, FQD_K_PAIRS, fqd::launch_grouped_candidates(items, c->ld_start.as<uint32_t>(), bucket_end, n_buckets, B,
                                                          c->gp_cands.as<uint64_t>(), cand_ctr, c->gp_cand_cap,
                                                          c->st, 0, skip));
@@ -559,7 +567,8 @@ static int grouped_tiles(fqd_ctx *c, uint64_t U, uint32_t d, uint32_t seg0, uint
                                                           which == 2 ? cb.list2 : cb.list, cb.counts + (which == 2 ? 4 : 0),
                                                           cb.tile_prefix, (uint32_t)U, seg0, c->urecs.as<uint32_t>(),
                                                           c->ulens.as<uint32_t>(), c->ks, d, nseg, c->edges.as<uint32_t>(),
-                                                          ctr + C64_EDGES, c->edge_cap, c->st));
+                                                          ctr + C64_EDGES, c->edge_cap, c->st,
+                                                          c->d_stats.as<fqd::PairStats>()));
     return FQD_OK;
 }
 
@@ -658,7 +667,7 @@ static int grouped_refine(fqd_ctx *c, const uint32_t *seg_hashes, uint64_t U, ui
     HIP_TRY(c, fqd::launch_group_verify_refined(c->gp_cands.as<uint64_t>(), cand_ctr, c->gp_cand_cap, c->urecs.as<uint32_t>(),
                                                 c->ulens.as<uint32_t>(), sh, nseg, seg_hashes, U, B, flags,
                                                 c->edges.as<uint32_t>(), ctr + C64_EDGES, c->edge_cap, ctr + C64_CAND_NEED,
-                                                c->st, d, accept));
+                                                c->st, d, accept, c->d_stats.as<fqd::PairStats>()));
     return FQD_OK;
 }
 
@@ -721,7 +730,7 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
     }
     if (!c->search_is_retry)
         c->route &= ~(FQD_ROUTE_SEARCH_GROUPED | FQD_ROUTE_SEARCH_SORT | FQD_ROUTE_SEARCH_EDIT | FQD_ROUTE_SEARCH_RETRIED |
-                      FQD_ROUTE_SEARCH_SMALL | FQD_ROUTE_SEARCH_SMALL_EDIT);
+                      FQD_ROUTE_SEARCH_SMALL | FQD_ROUTE_SEARCH_SMALL_EDIT | FQD_ROUTE_SEARCH_INPLACE);
     if (!grouped_first && !pass0_held) {
         FQD_TRY(zero_ctr64(c, C64_EDGES));
         HIP_TRY(c, hipMemsetAsync(c->d_stats.p, 0, FQD_STAT_SLOTS * sizeof(fqd::PairStats), c->st));
@@ -798,7 +807,16 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
         const bool fuse_passes = grouped && (seg_lo == 0 || pass0_held) && seg_hi == nseg && n_pass >= 2 && nseg <= 8 &&
                                  (uint64_t)n_pass * U < 0xFFFFFF00ull && !getenv("FQD_GROUP_NO_FUSED_PASSES");
         bool used_refine = false;
+        // Records of one uint4 need no candidate list: the pairs can be verified in the bucket's LDS (group_inplace.hip).
+        // Taken where the lists outgrow their budget (below; the context remembers) or pinned by FQD_GROUP_VERIFY=inplace;
+        // FQD_GROUP_VERIFY=list: never.
+        const char *pin_verify = getenv("FQD_GROUP_VERIFY");
+        const bool inplace_ok = n_shards == 1 && fqd::group_inplace_possible(sh, U, fuse_passes ? n_pass : 1u) &&
+                                !(pin_verify && !strcmp(pin_verify, "list"));
+        const bool inplace_pinned = inplace_ok && pin_verify && !strcmp(pin_verify, "inplace");
         for (int attempt = 0;; attempt++) {
+            const bool inplace = grouped && inplace_ok && (inplace_pinned || c->gp_inplace);
+            c->route = (c->route & ~FQD_ROUTE_SEARCH_INPLACE) | (inplace ? FQD_ROUTE_SEARCH_INPLACE : 0u);
             c->route |= (grouped ? FQD_ROUTE_SEARCH_GROUPED : small ? FQD_ROUTE_SEARCH_SMALL : FQD_ROUTE_SEARCH_SORT) |
                         (attempt ? FQD_ROUTE_SEARCH_RETRIED : 0u);
             if (small && seg_hi > seg_lo)
@@ -808,7 +826,8 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
                                c->d_ctr64.as<unsigned long long>() + C64_EDGES, c->edge_cap,
                                c->d_ctr64.as<unsigned long long>() + C64_CAND_NEED, c->d_stats.as<fqd::PairStats>(), c->st));
             if (fuse_passes && grouped) {
-                FQD_TRY(grouped_pass(c, c->seg_hashes.as<uint32_t>(), (uint64_t)n_pass * U, d, seg_lo, nseg, (uint32_t)U));
+                FQD_TRY(grouped_pass(c, c->seg_hashes.as<uint32_t>(), (uint64_t)n_pass * U, d, seg_lo, nseg, (uint32_t)U,
+                                     inplace));
                 if (c->gp_crowded_bits && (c->gp_tiles || !c->gp_fine_ok) && tiles_possible(c, nseg) &&
                     !getenv("FQD_GROUP_TILE_MAX_BUCKET")) {
                     // (every crowded bucket was put on list 2: no host round trip)
@@ -856,7 +875,7 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
                     FQD_TRY(sort_u32_pairs(c, c->sel_hash.as<uint32_t>(), c->sorted_hash.as<uint32_t>(),
                                            c->sel_uid.as<uint32_t>(), c->sorted_uid.as<uint32_t>(), m));
                 } else if (grouped) {
-                    FQD_TRY(grouped_pass(c, pass_hashes, U, d, s, nseg));
+                    FQD_TRY(grouped_pass(c, pass_hashes, U, d, s, nseg, 0, inplace));
                     continue;
                 } else {
                     if (!iota_ready) {
@@ -911,6 +930,13 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
                 HIP_TRY(c, c->edges.reserve((size_t)(now + now / 8 + 1024) * 8));
                 c->edge_cap = c->edges.cap / 8;
             }
+            // the candidate lists would outgrow their budget: one-uint4 records are verified in place from now on (before the
+            // whole-search retry below, so that it arrives there too); crowded families first go to the tiles, as before
+            const bool over_budget = cand_need > c->gp_cand_cap && cand_need > cand_budget;
+            const bool to_tiles = over_budget && used_refine && !c->gp_tiles && tiles_possible(c, nseg);
+            const bool to_inplace = over_budget && !to_tiles && inplace_ok && !inplace;
+            if (to_inplace)
+                c->gp_inplace = true;
             if (pass0_held) {
                 // the pairs of pass 0 are gone with the counters: the whole search once more, every pass here
                 c->route = (c->route & ~FQD_ROUTE_PASS0_CONTINUED) | FQD_ROUTE_SEARCH_RETRIED;
@@ -923,12 +949,13 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
                 return rc_again;
             }
             if (cand_need > c->gp_cand_cap) {
-                if (cand_need > cand_budget && used_refine && !c->gp_tiles && tiles_possible(c, nseg)) {
+                if (to_tiles) {
                     // the finer pieces left a crowded family in one piece (its candidate pairs are beyond every
                     // budget): from now on this context compares crowded buckets all pairs, tiled
                     c->gp_tiles = true;
                 } else if (cand_need > cand_budget) {
-                    grouped = false;
+                    if (!to_inplace)
+                        grouped = false;
                 } else {
                     c->gp_cands.release();
                     HIP_TRY(c, c->gp_cands.reserve((size_t)(cand_need + cand_need / 8 + 1024) * 8));

@@ -619,6 +619,16 @@ hipError_t launch_grouped_candidates(const uint32_t *items, const uint32_t *buck
                                      const uint8_t *skip = nullptr /* skip[b] != 0: bucket b is left out */,
                                      uint32_t give_up_over = 0, unsigned long long *cand_need = nullptr /* a bucket of more
                                      items is not walked; *cand_need is raised beyond every budget instead */);
+// group_inplace.hip -- records of one uint4: the candidates of every bucket verified where they are found, out of LDS
+// (no list, no budget); the inputs of launch_grouped_candidates plus those of launch_verify_candidates.
+// group_inplace_possible: what the kernel takes (n_pass_fused: passes in one partition, 0 or 1: one)
+bool group_inplace_possible(KeyShape sh, uint64_t U, uint32_t n_pass_fused);
+hipError_t launch_grouped_inplace(const uint32_t *items, const uint32_t *bucket_start, const uint32_t *bucket_end,
+                                  uint32_t n_buckets, uint32_t bucket_bits, const uint8_t *skip, uint32_t give_up_over,
+                                  unsigned long long *cand_need, const uint32_t *urecs, const uint32_t *ulens, KeyShape sh,
+                                  uint32_t d, uint32_t seg, uint32_t nseg, uint32_t *edges,
+                                  unsigned long long *edge_count, uint64_t edge_cap, PairStats *stats, hipStream_t st,
+                                  uint32_t fused_U = 0);
 bool group_tiles_possible(KeyShape sh, uint32_t nseg);
 // crowded buckets of a search at distance d <= 3 (group.hip "crowded buckets"): marked, skipped by the candidate kernel,
 // their keys matched on finer pieces. group_fine_items(d): items a crowded key files (0: no refinement at that distance);
@@ -637,12 +647,13 @@ hipError_t launch_group_crowded_tiles(const uint32_t *items, const uint32_t *buc
                                       const uint32_t *list, const unsigned long long *counts, unsigned long long *tile_prefix,
                                       uint32_t fused_U, uint32_t seg0, const uint32_t *urecs, const uint32_t *ulens, KeyShape sh,
                                       uint32_t d, uint32_t nseg, uint32_t *edges, unsigned long long *edge_count,
-                                      uint64_t edge_cap, hipStream_t st);
+                                      uint64_t edge_cap, hipStream_t st, PairStats *stats = nullptr);
 hipError_t launch_group_verify_refined(const uint64_t *cands, const unsigned long long *cand_count, uint64_t cand_cap,
                                        const uint32_t *urecs, const uint32_t *ulens, KeyShape sh, uint32_t nseg,
                                        const uint32_t *seg_hashes, uint64_t U, uint32_t bucket_bits,
                                        const uint8_t *crowded, uint32_t *edges, unsigned long long *edge_count,
-                                       uint64_t edge_cap, unsigned long long *cand_need, hipStream_t st, uint32_t d, uint32_t accept = 3);
+                                       uint64_t edge_cap, unsigned long long *cand_need, hipStream_t st, uint32_t d, uint32_t accept = 3,
+                                       PairStats *stats = nullptr);
 hipError_t launch_verify_candidates(const uint64_t *cands, const unsigned long long *cand_count, uint64_t cand_cap,
                                     const uint32_t *urecs, const uint32_t *ulens, KeyShape sh, uint32_t d, uint32_t seg,
                                     uint32_t nseg, uint32_t *edges, unsigned long long *edge_count, uint64_t edge_cap,

@@ -863,7 +863,8 @@ __global__ __launch_bounds__(256) void gp_verify_refined_kernel(
     const uint32_t *__restrict__ urecs, const uint32_t *__restrict__ ulens, KeyShape sh, uint32_t nseg,
     const uint32_t *__restrict__ seg_hashes /* [nseg][U] */, uint64_t U, uint32_t bucket_bits,
     const uint8_t *__restrict__ crowded, uint32_t *__restrict__ edges, unsigned long long *__restrict__ edge_count,
-    uint64_t edge_cap, unsigned long long *__restrict__ cand_need, uint32_t d, uint32_t accept /* bits of crowded[] values whose buckets this refinement answers for */)
+    uint64_t edge_cap, unsigned long long *__restrict__ cand_need, uint32_t d, uint32_t accept /* bits of crowded[] values whose buckets this refinement answers for */,
+    fqd::PairStats *__restrict__ stats /* NULL, or stats[slot].edges += pairs reported */)
 {
     const uint32_t list = blockIdx.x % GP_LISTS, part = blockIdx.x / GP_LISTS, parts = gridDim.x / GP_LISTS;
     const unsigned long long filled = cand_count[(size_t)list * 8];
@@ -971,8 +972,11 @@ __global__ __launch_bounds__(256) void gp_verify_refined_kernel(
         }
         __syncthreads();
         const uint32_t n_hit = s_n;
-        if (threadIdx.x == 0 && n_hit)
+        if (threadIdx.x == 0 && n_hit) {
             s_at = atomicAdd(edge_count, (unsigned long long)n_hit);
+            if (stats)
+                atomicAdd(&stats[blockIdx.x % FQD_STAT_SLOTS].edges, (unsigned long long)n_hit);
+        }
         __syncthreads();
         if (n_hit) {
             const unsigned long long at = s_at;
@@ -1023,7 +1027,8 @@ __global__ __launch_bounds__(CT_TS) void gp_crowded_tiles_kernel(
     const uint32_t *__restrict__ list, const unsigned long long *__restrict__ counts,
     const unsigned long long *__restrict__ tile_prefix, uint32_t fused_U, uint32_t seg0,
     const uint32_t *__restrict__ urecs, const uint32_t *__restrict__ ulens, KeyShape sh, uint32_t d, uint32_t nseg,
-    uint32_t *__restrict__ edges, unsigned long long *__restrict__ edge_count, uint64_t edge_cap)
+    uint32_t *__restrict__ edges, unsigned long long *__restrict__ edge_count, uint64_t edge_cap,
+    fqd::PairStats *__restrict__ stats /* NULL, or stats[slot].edges += pairs reported */)
 {
     constexpr uint32_t ROW4 = Q4 + 1, WMAX = Q4 * 4 / K;        // (words of 32 bases a record of Q4 uint4 can hold)
     __shared__ uint4 rec_j[CT_TS * ROW4];
@@ -1033,6 +1038,7 @@ __global__ __launch_bounds__(CT_TS) void gp_crowded_tiles_kernel(
     __shared__ uint32_t s_mask[WMAX][8];                  // keys of ONE length: the bits of word w inside main segment s
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t W = sh.words;
+    uint32_t my_hits = 0;
     if (lane == 0)
         s_wn[wave] = 0;
     for (uint32_t x = tid; x < WMAX * 8u; x += CT_TS) {
@@ -1171,6 +1177,7 @@ __global__ __launch_bounds__(CT_TS) void gp_crowded_tiles_kernel(
                     wbuf[wave][have + (uint32_t)__popcll(hm & fqd_lanemask_lt())] = make_uint2(min(my_uid, uk), max(my_uid, uk));
                 if (lane == 0)
                     s_wn[wave] = have + n;
+                my_hits += hit ? 1u : 0u;
             }
         }
     }
@@ -1178,6 +1185,12 @@ __global__ __launch_bounds__(CT_TS) void gp_crowded_tiles_kernel(
     const uint32_t left = s_wn[wave];
     if (left)
         flush(left);
+    if (stats) {
+        for (int o = 32; o; o >>= 1)
+            my_hits += __shfl_xor(my_hits, o);
+        if (lane == 0 && my_hits)
+            atomicAdd(&stats[(blockIdx.x * (CT_TS / 64) + wave) % FQD_STAT_SLOTS].edges, (unsigned long long)my_hits);
+    }
 }
 
 }  // namespace
@@ -1364,7 +1377,7 @@ hipError_t launch_group_crowded_tiles(const uint32_t *items, const uint32_t *buc
                                       const uint32_t *list, const unsigned long long *counts, unsigned long long *tile_prefix,
                                       uint32_t fused_U, uint32_t seg0, const uint32_t *urecs, const uint32_t *ulens, KeyShape sh,
                                       uint32_t d, uint32_t nseg, uint32_t *edges, unsigned long long *edge_count,
-                                      uint64_t edge_cap, hipStream_t st)
+                                      uint64_t edge_cap, hipStream_t st, PairStats *stats)
 {
     const uint32_t q4 = sh.stride / 4;
     if (sh.stride > 32 || (sh.stride & 3u) || (q4 & (q4 - 1)) || nseg > 8 || sh.planes < 2 || sh.planes > 3)
@@ -1373,7 +1386,7 @@ hipError_t launch_group_crowded_tiles(const uint32_t *items, const uint32_t *buc
 #define FQD_TILES(KK, QQ)                                                                                               \
     gp_crowded_tiles_kernel<KK, QQ><<<8192, CT_TS, 0, st>>>(reinterpret_cast<const uint2 *>(items), bucket_start,      \
                                                             bucket_end, list, counts, tile_prefix, fused_U, seg0, urecs, \
-                                                            ulens, sh, d, nseg, edges, edge_count, edge_cap)
+                                                            ulens, sh, d, nseg, edges, edge_count, edge_cap, stats)
     if (sh.planes == 3) {
         if (q4 == 1) FQD_TILES(3, 1); else if (q4 == 2) FQD_TILES(3, 2); else if (q4 == 4) FQD_TILES(3, 4); else FQD_TILES(3, 8);
     } else {
@@ -1395,14 +1408,14 @@ hipError_t launch_group_verify_refined(const uint64_t *cands, const unsigned lon
                                        const uint32_t *seg_hashes, uint64_t U, uint32_t bucket_bits,
                                        const uint8_t *crowded, uint32_t *edges, unsigned long long *edge_count,
                                        uint64_t edge_cap, unsigned long long *cand_need, hipStream_t st, uint32_t d,
-                                       uint32_t accept)
+                                       uint32_t accept, PairStats *stats)
 {
     if (!gp_fine_sets(d))
         return hipErrorInvalidValue;
     gp_verify_refined_kernel<<<GP_LISTS * 16, 256, 0, st>>>(reinterpret_cast<const uint2 *>(cands), cand_count,
                                                             cand_cap / GP_LISTS, urecs, ulens, sh, nseg, seg_hashes, U,
                                                             bucket_bits, crowded, edges, edge_count, edge_cap, cand_need, d,
-                                                            accept);
+                                                            accept, stats);
     return hipGetLastError();
 }
 

@@ -106,6 +106,8 @@ typedef struct fqd_summary {
                                             * keys grouped by segment hash in LDS tables, no sort (small_search.hip)        */
 #define FQD_ROUTE_SEARCH_SMALL_EDIT 0x40000u /* Levenshtein search (d = 1..3) of a table under 32 768 keys: index and probe
                                             * items into per-bin slabs, one workgroup per bin (small_edit_search.hip)       */
+#define FQD_ROUTE_SEARCH_INPLACE  0x80000u /* with SEARCH_GROUPED, records of one uint4: each bucket's pairs verified in
+                                            * LDS where they are found, no candidate list (group_inplace.hip)             */
 int fqd_get_route(const fqd_ctx *ctx, uint32_t *route);
 
 /* Packed-key geometry chosen by fqd_pack_keys (DESIGN.md "data layout"). */
