@@ -728,6 +728,59 @@ int collapse_pairs(fqd_ctx *c, const uint32_t *d_w, IdSource d_ids, bool *done)
     return FQD_OK;
 }
 
+// The whole collapse of a small input in two launches back to back (small_collapse.hip) and one read-back: records
+// of any size, fixed-length or ragged, below SMALL_COLLAPSE_CUTOFF reads. d_ids: a plain id array or none (the
+// stamped ids have been taken out of the records). The rows come out ordered by (hash bin, first position): two jobs
+// over one input number their keys alike. *done = false: not applicable, or a bin overflowed -- the caller goes on
+// to the pairs or the sort path.
+constexpr uint64_t SMALL_COLLAPSE_CUTOFF = 65536;
+int collapse_small(fqd_ctx *c, const uint32_t *d_w, IdSource d_ids, bool *done)
+{
+    *done = false;
+    const uint64_t n = c->n;
+    const KeyShape sh = c->ks;
+    const char *force = getenv("FQD_COLLAPSE");  // "small" pins this path for up to 2^20 reads; any other pin skips it
+    if (force && strcmp(force, "small"))
+        return FQD_OK;
+    if (getenv("FQD_HASH_BITS"))                 // (the sort path's knob: whoever sets it wants that path)
+        return FQD_OK;
+    if ((sh.stride & 3u) || sh.stride > 256 || d_ids.stamped || n < 1 ||
+        n >= (force ? fqd::SMALL_COLLAPSE_MAX_N : SMALL_COLLAPSE_CUTOFF))
+        return FQD_OK;
+    FQD_TRY(ensure_hashes(c));
+    HIP_TRY(c, c->sc_park.reserve(fqd::small_collapse_park_bytes(n)));
+    if (!c->sc_ctr.p || !c->sc_ctr_clean) {
+        HIP_TRY(c, c->sc_ctr.reserve(fqd::SMALL_COLLAPSE_CTR_WORDS * 4));
+        HIP_TRY(c, hipMemsetAsync(c->sc_ctr.p, 0, fqd::SMALL_COLLAPSE_CTR_WORDS * 4, c->st));
+    }
+    c->sc_ctr_clean = false;                     // (until the kernel has been seen to finish)
+    // n rows up front: no second read-back to size the table
+    HIP_TRY(c, c->urecs.reserve(n * sh.stride * 4 + 16));
+    HIP_TRY(c, c->ulens.reserve(n * 4 + 16));
+    HIP_TRY(c, c->ucounts.reserve(n * 4 + 16));
+    HIP_TRY(c, c->ufirst.reserve(n * 8 + 64));
+    KTIME(c, FQD_K_SMALL_COLLAPSE,
+          fqd::launch_small_collapse(c->hashes.as<uint32_t>(), c->recs.as<uint32_t>(), c->lens.as<uint32_t>(), n, sh, d_w,
+                                     d_ids.ids64, c->urecs.as<uint32_t>(), c->ulens.as<uint32_t>(),
+                                     c->ucounts.as<uint32_t>(), c->ufirst.as<uint64_t>(), c->sc_ctr.as<uint32_t>(),
+                                     c->sc_park.as<uint32_t>(), c->st));
+    uint32_t res[4] = {0, 0, 0, 0};              // rows, overflow, counted weight (u64)
+    void *dst = c->h_pin ? c->h_pin : (void *)res;
+    HIP_TRY(c, hipMemcpyAsync(dst, c->sc_ctr.as<uint32_t>() + 8, sizeof res, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(c, stream_wait(c->st));
+    if (dst != (void *)res)
+        memcpy(res, dst, sizeof res);
+    c->sc_ctr_clean = true;
+    if (res[1])
+        return FQD_OK;                           // (c->U and c->n_counted are still 0)
+    unsigned long long counted = 0;
+    memcpy(&counted, res + 2, 8);
+    c->U = res[0];
+    c->n_counted = counted;
+    *done = true;
+    return FQD_OK;
+}
+
 // Levenshtein neighbour search for the general case (edit.hip): index/probe records ->
 // sort -> candidate pairs -> sort/unique -> banded-DP verification.
 
@@ -836,7 +889,7 @@ void fqd_destroy(fqd_ctx *c)
                       &c->t_mark_incl, &c->t_stats, &c->t_seed, &c->t_heads, &c->t_heads_incl, &c->t_member_uids,
                       &c->t_offsets, &c->store_alive, &c->st_recs, &c->st_lens, &c->st_counts, &c->st_first,
                       &c->st_comb_recs, &c->st_comb_lens, &c->st_comb_w, &c->st_comb_ids, &c->eg_tables, &c->eg_per_key,
-                      &c->eg_per_key_incl, &c->ld_side, &c->ld_side_table};
+                      &c->eg_per_key_incl, &c->ld_side, &c->ld_side_table, &c->sc_ctr, &c->sc_park};
     for (DevBuf *b : bufs)
         b->release();
     fqd_api_fastq_release(c);
@@ -1109,6 +1162,23 @@ static int collapse_impl(fqd_ctx *c, const uint32_t *weights, int mem, IdSource 
         IdSource plain;
         plain.ids64 = c->in_read_ids.as<uint64_t>();
         ids = plain;
+    }
+    bool small_done = false;
+    FQD_TRY(collapse_small(c, weights ? d_w : nullptr, ids, &small_done));
+    if (small_done) {
+        timer.stop();
+        c->route |= FQD_ROUTE_COLLAPSE_SMALL;
+        c->collapse_path = 4;
+        c->urecs_len_pad = false;
+        c->seg_hashes_nseg = 0;
+        c->pass0_done = false;
+        c->collapsed = true;
+        c->first_distinct = true;
+        set_id_range(c, read_ids ? id_limit : n);
+        c->stage = ST_UNIQUE;
+        if (n_unique)
+            *n_unique = c->U;
+        return FQD_OK;
     }
     bool pairs_done = false;
     FQD_TRY(collapse_pairs(c, weights ? d_w : nullptr, ids, &pairs_done));

@@ -156,7 +156,10 @@ struct fqd_ctx {
     DevBuf ld_hist, ld_hist_incl, ld_start, ld_cursor, ld_part, ld_tmp_rec, ld_tmp_count, ld_tmp_first, ld_unique,
         ld_unique_incl;
     uint32_t route = 0;     // FQD_ROUTE_* bits of the job in progress / the last one (fqd_get_route)
-    int collapse_path = 0;  // 1: LDS bucket dedupe, 2: sort + verify (last fqd_collapse)
+    int collapse_path = 0;  // 1: LDS bucket dedupe, 2: sort + verify, 3: (hash, position) pairs, 4: one launch (last fqd_collapse)
+    DevBuf sc_ctr;          // collapse_small: the kernel's counters and results (fqd::SMALL_COLLAPSE_CTR_WORDS)
+    bool sc_ctr_clean = false;   // ... which its last launch left zeroed (false: cleared before the next one)
+    DevBuf sc_park;         // ... and what its two launches hand over (fqd::small_collapse_park_bytes)
     // stage 3
     uint64_t E = 0, edge_cap = 0;
     DevBuf seg_hashes, sorted_hash, sorted_uid, uid_iota, edges, sel_hash, sel_uid;

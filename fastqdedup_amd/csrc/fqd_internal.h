@@ -550,6 +550,24 @@ SmallEdit small_edit_plan(uint64_t U, KeyShape sh, uint32_t d);
 hipError_t launch_small_edit_items(const SmallEdit &A, KeyShape sh, hipStream_t st);
 hipError_t launch_small_edit_search(const SmallEdit &A, KeyShape sh, hipStream_t st);
 
+// small_collapse.hip -- the whole collapse of a small input: a workgroup per hash bin, an LDS table of the bin's
+// distinct keys, no sort and no scan, and a small second launch that writes the table ordered by (bin, first
+// position). hashes: the reads' record hashes, 16-byte aligned and readable up to the
+// end of their last uint4; lens / weights / read_ids may be NULL (fixed length / weight 1 / id = position); the four
+// output arrays hold n rows. ctr: SMALL_COLLAPSE_CTR_WORDS words that were zero before the context's first launch --
+// the kernel leaves words 0..7 zero again and, in words 8..11, the rows written, the overflow word (!= 0: a bin held more
+// distinct keys or colliding reads than its workgroup takes, nothing of the output counts) and the counted weight (u64).
+// park: small_collapse_park_bytes(n) bytes, 8-byte aligned, of any content: the bins' row counts and the rows'
+// (position, count) between the two launches.
+constexpr uint32_t SMALL_COLLAPSE_CTR_WORDS = 16;
+constexpr uint64_t SMALL_COLLAPSE_MAX_N = 1ull << 20;
+constexpr uint32_t SMALL_COLLAPSE_MAX_BINS = 2048;         // MAX_N / 512 reads per bin
+inline size_t small_collapse_park_bytes(uint64_t n) { return (size_t)SMALL_COLLAPSE_MAX_BINS * 8 + (size_t)n * 8; }
+hipError_t launch_small_collapse(const uint32_t *hashes, const uint32_t *recs, const uint32_t *lens, uint64_t n,
+                                 KeyShape sh, const uint32_t *weights, const uint64_t *read_ids, uint32_t *urecs,
+                                 uint32_t *ulens, uint32_t *ucounts, uint64_t *ufirst, uint32_t *ctr, uint32_t *park,
+                                 hipStream_t st);
+
 // edit.hip -- Levenshtein neighbour search + contains
 hipError_t launch_len_present(const uint32_t *ulens, uint64_t U, KeyShape sh, uint8_t *len_present, hipStream_t st);
 hipError_t launch_edit_records(const uint32_t *urecs, const uint32_t *ulens, uint64_t U, KeyShape sh, uint32_t d,

@@ -108,6 +108,9 @@ typedef struct fqd_summary {
                                             * items into per-bin slabs, one workgroup per bin (small_edit_search.hip)       */
 #define FQD_ROUTE_SEARCH_INPLACE  0x80000u /* with SEARCH_GROUPED, records of one uint4: each bucket's pairs verified in
                                             * LDS where they are found, no candidate list (group_inplace.hip)             */
+#define FQD_ROUTE_COLLAPSE_SMALL  0x100000u /* collapse of an input under 65 536 reads without a sort: a workgroup per hash bin
+                                            * with the bin's distinct keys in an LDS table, rows ordered by (bin, first
+                                            * position) (small_collapse.hip)                                                 */
 int fqd_get_route(const fqd_ctx *ctx, uint32_t *route);
 
 /* Packed-key geometry chosen by fqd_pack_keys (DESIGN.md "data layout"). */
@@ -554,7 +557,8 @@ int fqd_stage_times(fqd_ctx *ctx, float *ms /* FQD_T_COUNT */, uint32_t *launche
 #define FQD_K_FASTQ_GATHER       25   /* key bytes + quality gate */
 #define FQD_K_FASTQ_EMIT_SIZES   26   /* the FASTQ emit: output size of every kept record of a chunk, */
 #define FQD_K_FASTQ_EMIT_COPY    27   /* the output bytes, a tile per workgroup */
-#define FQD_K_COUNT         28
+#define FQD_K_SMALL_COLLAPSE     28   /* the collapse of a small input, both launches (small_collapse.hip) */
+#define FQD_K_COUNT         29
 int fqd_kernel_times(fqd_ctx *ctx, float *ms /* FQD_K_COUNT */, uint32_t *launches /* FQD_K_COUNT */,
                      int reset);
 /* What is timed. Timers never synchronise the host: they are event pairs recorded while the work
