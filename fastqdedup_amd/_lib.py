@@ -911,7 +911,7 @@ class Context:
                "uf_flatten_kernel", "dissect_round_kernel", "gp_hist_kernel", "gp_scatter_kernel", "verify_candidates_kernel", "kept_flags_kernel",
                "part_scatter12_kernel", "bucket_dedupe12_kernel", "fastq_line_count_kernel", "fastq_line_scatter_kernel",
                "fastq_records_kernel", "fastq_mates_kernel", "fastq_key_lens_kernel", "fastq_gather_kernel",
-               "fastq_emit_sizes_kernel", "fastq_emit_copy_kernel", "small_collapse_kernel"]
+               "fastq_emit_sizes_kernel", "fastq_emit_copy_kernel", "small_collapse_kernel", "small_graph_kernel"]
 
     def kernel_times(self, reset: bool = True):
         """{kernel: (ms summed over launches, launches)} since the last reset."""
@@ -977,7 +977,7 @@ class Context:
                   "search_sort": 0x200, "search_edit": 0x400, "search_retried": 0x800, "pass0_continued": 0x1000,
                   "spill_list": 0x2000, "search_refined": 0x4000, "one_kernel_collapse": 0x8000, "search_tiles": 0x10000,
                   "search_small": 0x20000, "search_small_edit": 0x40000,
-                  "search_inplace": 0x80000, "collapse_small": 0x100000}
+                  "search_inplace": 0x80000, "collapse_small": 0x100000, "graph_small": 0x200000}
 
     def route(self) -> dict:
         """Which way the last job took (fqd_get_route): {name: bool} over the FQD_ROUTE_* bits."""

@@ -2111,9 +2111,32 @@ static int cluster_tail(fqd_ctx *c, int max_distance, int metric, int method, fq
     }
     c->pre_init = c->pre_init_closed = false;
     c->preinit_method = (method >= 0 && method <= 2 && method != FQD_METHOD_HIGHEST_COUNT && !getenv("FQD_NO_PREINIT")) ? method : -1;
+    // a small table's graph stage is ONE launch (small_graph.hip): nothing to set up behind the search, nothing to fork
+    c->search_shards = 1;
+    const bool small_graph = fqd_api_graph_small_planned(c);
+    if (small_graph)
+        c->preinit_method = -1;
     const int rc_search = fqd_find_edges(c, max_distance, metric, 0, 1, nullptr);
     c->preinit_method = -1;
     FQD_TRY(rc_search);
+    c->route &= ~FQD_ROUTE_GRAPH_SMALL;
+    if (small_graph) {
+        bool done = false;
+        FQD_TRY(fqd_api_graph_small_all(c, method, &done));
+        if (done) {
+            c->ms[FQD_T_COMPONENTS] = 0;
+            c->tpending[FQD_T_COMPONENTS] = false;
+            if (out) {
+                out->n_reads = c->n;
+                out->n_counted = c->n_counted;
+                out->n_unique = c->U;
+                out->n_edges = c->E;
+                out->n_clusters = c->n_clusters;
+                out->n_kept = c->n_kept;
+            }
+            return FQD_OK;
+        }
+    }
     // no host round trip between components and dissection; labels are flattened only if read
     // (directional, closed form: the dissection never reads the labels -- the union-find runs beside its first pass)
     const bool beside = method == FQD_METHOD_DIRECTIONAL && c->collapsed && !getenv("FQD_DIRECTIONAL_ROUNDS") &&

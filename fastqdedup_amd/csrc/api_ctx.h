@@ -228,6 +228,7 @@ struct fqd_ctx {
     bool fast_probe = false;
     uint32_t last_spill_used = 0;  // records the last fused job sent to its spill list
     bool heavy_keys = false;       // a fused attempt ended on a full slab: from now on with the spill list (api.hip pack_collapse_fused_once)
+    uint32_t search_shards = 1;    // n_shards of the search that made the edge list (1: imported edges; the small graph route wants one shard)
     int last_search_d = 0;         // max_distance of the last neighbour search (the closed-form dissection: pass 1b from d = 2 on)
     bool uf_sampled = false;       // the union-find met a giant component on this context: every 16th edge first (graph.hip uf_union_kernel)
     bool join_pending = false;     // the components were queued on st_side: ev_join must be waited for before their counter is read
@@ -544,6 +545,8 @@ int fqd_api_flat_labels(fqd_ctx *c);                       // api_graph.hip
 // the collapse over c->recs with DEVICE weights and ids (api.hip)
 int fqd_api_collapse_device(fqd_ctx *c, const uint32_t *d_weights, IdSource ids, uint64_t id_limit, uint64_t *n_unique);
 int fqd_api_graph_preinit(fqd_ctx *c, int method);          // api_graph.hip
+bool fqd_api_graph_small_planned(const fqd_ctx *c);         // api_graph.hip: the one-launch graph stage will be taken (but for the edge count)
+int fqd_api_graph_small_all(fqd_ctx *c, int method, bool *done);   // api_graph.hip
 void fqd_api_fastq_release(fqd_ctx *c);                     // api_fastq.hip
 extern "C" int fqd_api_partition_pairs(fqd_ctx *c, const uint32_t *keys, uint64_t N, uint32_t B, bool slabs,
                                        const uint32_t **items_out, const uint32_t **bucket_end_out,

@@ -323,6 +323,7 @@ int fqd_import_edges(fqd_ctx *c, const uint32_t *uv, uint64_t E, int mem)
     if (mem != FQD_DEVICE)
         HIP_TRY(c, stream_wait(c->st));
     c->E = E;
+    c->search_shards = 1;
     c->stage = ST_EDGES;
     return FQD_OK;
 }

@@ -145,6 +145,102 @@ static int graph_preinit(fqd_ctx *c, int method)
     return FQD_OK;
 }
 
+// ---- the one-launch route of a small table (small_graph.hip) ------------------------------------------------------
+// The ids the kept list covers: [base, base + window)
+static void kept_window(const fqd_ctx *c, uint64_t *base, uint64_t *window)
+{
+    *base = 0;
+    *window = c->id_limit;
+    if (c->id_hi != ~0ull) {
+        *base = c->id_lo;
+        *window = std::min(*window > *base ? *window - *base : 0, c->id_hi - c->id_lo);
+    }
+}
+
+// Decided on the host, nothing read back: everything but the edge count (known once the search has run).
+// FQD_GRAPH=wide: never; FQD_GRAPH=small: up to SMALL_GRAPH_MAX_U_GLOBAL keys, best[] and the state bytes in global memory
+// above SMALL_GRAPH_LDS_U.
+static bool graph_small_planned(const fqd_ctx *c)
+{
+    const char *pin = getenv("FQD_GRAPH");
+    if (pin && !strcmp(pin, "wide"))
+        return false;
+    const uint64_t U = c->U;
+    if (!U || U > (pin && !strcmp(pin, "small") ? fqd::SMALL_GRAPH_MAX_U_GLOBAL : fqd::SMALL_GRAPH_MAX_U))
+        return false;
+    if (c->search_shards != 1 || (c->store_removed && c->store_table_U == U) || c->owner_rule.parts || c->drop_after_n)
+        return false;
+    if (c->id_hi == ~0ull && c->id_lo)
+        return false;
+    uint64_t base, window;
+    kept_window(c, &base, &window);
+    // (list_kept's map or id-bin branch: distinct first-holder ids in a window not much larger than the table)
+    return c->first_distinct && window <= 32 * U && window <= fqd::SMALL_GRAPH_MAX_WINDOW && !getenv("FQD_KEPT_BY_SORT");
+}
+
+static bool graph_small_takes(const fqd_ctx *c) { return graph_small_planned(c) && c->E <= fqd::SMALL_GRAPH_MAX_E; }
+
+// phases: 1 union + flatten, 2 dissect + list (labels flat in global memory), 3 all four
+static int graph_small_queue(fqd_ctx *c, int method, uint32_t phases)
+{
+    const uint64_t U = c->U;
+    if (c->join_pending) {
+        HIP_TRY(c, hipStreamWaitEvent(c->st, c->ev_join, 0));
+        c->join_pending = false;
+    }
+    c->pre_init = c->pre_init_closed = c->pre_nodes = c->pre_zero_tail = c->pass1_done = false;
+    HIP_TRY(c, c->labels.reserve(U * 4 + 16));
+    fqd::SmallGraph A{};
+    A.U = (uint32_t)U;
+    A.E = (uint32_t)c->E;
+    A.method = (uint32_t)method;
+    A.phases = phases;
+    A.closed_form = method == FQD_METHOD_DIRECTIONAL && c->collapsed && !getenv("FQD_DIRECTIONAL_ROUNDS");
+    A.edges = c->edges.as<uint32_t>();
+    A.ucounts = c->ucounts.as<uint32_t>();
+    A.urecs = c->urecs.as<uint32_t>();
+    A.ulens = c->ulens.as<uint32_t>();
+    A.ufirst = c->ufirst.as<uint64_t>();
+    A.labels = c->labels.as<uint32_t>();
+    A.ctr64 = c->d_ctr64.as<unsigned long long>() + C64_ROOTS;    // C64_ROOTS, C64_SUM, and the ids listed behind them
+    if (phases & 2u) {
+        kept_window(c, &A.base, &A.window);
+        HIP_TRY(c, c->kept.reserve(U + 16));
+        A.kept = c->kept.as<uint8_t>();
+        c->n_kept = c->n_listed = 0;
+        c->kept_list_lost = false;
+        // the list goes straight into the caller's buffer when one was announced and is large enough for any outcome
+        c->kept_in_out = c->kept_out && c->kept_out_cap >= std::min(A.window, U);
+        A.list_out = c->kept_out;
+        if (!c->kept_in_out) {
+            HIP_TRY(c, c->kept_ids_sorted.reserve(std::min(A.window, U) * 8 + 16));
+            A.list_out = c->kept_ids_sorted.as<uint64_t>();
+        }
+        if (U > fqd::SMALL_GRAPH_LDS_U) {
+            HIP_TRY(c, c->best.reserve(U * 4 + 16));
+            HIP_TRY(c, c->state.reserve(U + 16));
+            A.g_best = c->best.as<uint32_t>();
+            A.g_state = c->state.as<uint8_t>();
+        }
+    }
+    KTIME(c, FQD_K_SMALL_GRAPH, fqd::launch_small_graph(A, c->ks, c->st));
+    if (phases & 1u)
+        c->labels_flat = true;
+    return FQD_OK;
+}
+
+// the dissection's one read-back: components, kept keys, ids listed
+static int graph_small_results(fqd_ctx *c)
+{
+    unsigned long long r[3] = {0, 0, 0};
+    FQD_TRY(read_ctr64(c, C64_ROOTS, r, 3));
+    c->roots_seen = r[0];
+    c->n_kept = r[1];
+    c->n_listed = r[2];
+    c->route |= FQD_ROUTE_GRAPH_SMALL;
+    return FQD_OK;
+}
+
 int fqd_components(fqd_ctx *c, uint64_t *n_clusters)
 {
     FQD_TRY(bind(c));
@@ -152,7 +248,13 @@ int fqd_components(fqd_ctx *c, uint64_t *n_clusters)
         return fail(c, FQD_E_STATE, "fqd_components before fqd_find_edges/fqd_import_edges");
     c->stage = ST_EDGES;
     StageTimer timer(c, FQD_T_COMPONENTS);
-    FQD_TRY(components_queue(c, false));   // labels are flattened when somebody reads them
+    c->route &= ~FQD_ROUTE_GRAPH_SMALL;
+    if (graph_small_takes(c)) {
+        FQD_TRY(graph_small_queue(c, 0, 1u));
+        c->route |= FQD_ROUTE_GRAPH_SMALL;
+    } else {
+        FQD_TRY(components_queue(c, false));   // labels are flattened when somebody reads them
+    }
     unsigned long long roots = 0;
     FQD_TRY(read_ctr64(c, C64_ROOTS, &roots));
     timer.stop();
@@ -318,6 +420,19 @@ int fqd_dissect(fqd_ctx *c, int method, uint64_t *n_kept)
     const uint64_t U = c->U, E = c->E;
     const KeyShape sh = c->ks;
     StageTimer timer(c, FQD_T_DISSECT);
+    if (graph_small_takes(c)) {
+        // one launch on flat labels, one read-back (small_graph.hip); best[], state[] and root_taint[] are not written --
+        // nothing reads them after a dissection
+        FQD_TRY(ensure_flat_labels(c));
+        FQD_TRY(graph_small_queue(c, method, 2u));
+        FQD_TRY(graph_small_results(c));
+        timer.stop();
+        c->stage = ST_KEPT;
+        if (n_kept)
+            *n_kept = c->n_kept;
+        return FQD_OK;
+    }
+    c->route &= ~FQD_ROUTE_GRAPH_SMALL;
     HIP_TRY(c, c->best.reserve(U * 4 + 16));
     HIP_TRY(c, c->state.reserve(U + 16));
     HIP_TRY(c, c->kept.reserve(U + 16));
@@ -708,3 +823,21 @@ int fqd_list_kept_except(fqd_ctx *c, const uint32_t *dropped, uint64_t n_dropped
 int fqd_api_components_queue(fqd_ctx *c, bool flatten, bool on_side) { return components_queue(c, flatten, on_side); }
 int fqd_api_flat_labels(fqd_ctx *c) { return ensure_flat_labels(c); }
 int fqd_api_graph_preinit(fqd_ctx *c, int method) { return graph_preinit(c, method); }
+bool fqd_api_graph_small_planned(const fqd_ctx *c) { return graph_small_planned(c); }
+
+// fqd_cluster[_keys]: the whole graph stage of a small table as one launch and one read-back. *done = false: the table
+// is not eligible after all (more than 2^20 edges), nothing was queued.
+int fqd_api_graph_small_all(fqd_ctx *c, int method, bool *done)
+{
+    *done = false;
+    if (method < 0 || method > 2 || !graph_small_takes(c))
+        return FQD_OK;
+    StageTimer timer(c, FQD_T_DISSECT);
+    FQD_TRY(graph_small_queue(c, method, 3u));
+    FQD_TRY(graph_small_results(c));
+    timer.stop();
+    c->n_clusters = c->roots_seen;
+    c->stage = ST_KEPT;
+    *done = true;
+    return FQD_OK;
+}

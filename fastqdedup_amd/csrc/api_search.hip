@@ -684,6 +684,7 @@ static int find_edges_impl(fqd_ctx *c, int max_distance, int metric, uint32_t sh
     c->last_search_d = max_distance;
     if (n_shards == 0 || shard >= n_shards)
         return fail(c, FQD_E_VALUE, "bad shard");
+    c->search_shards = n_shards;
     const KeyShape sh = c->ks;
     // Levenshtein <= 1 between keys of ONE length is Hamming <= 1 (an indel changes the length):
     // that case shares the Hamming search; everything else takes the bucketed edit search.

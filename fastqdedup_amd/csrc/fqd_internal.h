@@ -568,6 +568,33 @@ hipError_t launch_small_collapse(const uint32_t *hashes, const uint32_t *recs, c
                                  uint32_t *ulens, uint32_t *ucounts, uint64_t *ufirst, uint32_t *ctr, uint32_t *park,
                                  hipStream_t st);
 
+// small_graph.hip -- components, dissection, kept flags and the ascending kept-id list of a small unique table in ONE
+// launch of ONE workgroup, everything in its LDS. phases: 1 union + flatten (labels[], ctr64[0] = components),
+// 2 dissect + list on labels already flat (kept[], list_out[], ctr64[1] = kept keys, ctr64[2] = ids listed), 3 both.
+// Ids listed: first holders of kept keys in [base, base + window); list_out holds min(window, U) ids. ctr64: three
+// consecutive words, left with plain stores. Above SMALL_GRAPH_LDS_U keys best[] and the state bytes do not fit the
+// LDS: g_best (U words) and g_state (U bytes rounded up to words) in global memory then.
+// SMALL_GRAPH_MAX_U: the cut-off without a pin -- the largest measured table at which the route beat the wide one for
+// every method (at 7 810 keys of 300 nt highest_count lost: its ties walk rows word by word).
+constexpr uint32_t SMALL_GRAPH_MAX_U = 5854, SMALL_GRAPH_LDS_U = 8192, SMALL_GRAPH_MAX_U_GLOBAL = 16384;
+constexpr uint64_t SMALL_GRAPH_MAX_E = 1ull << 20, SMALL_GRAPH_MAX_WINDOW = 1ull << 18;
+struct SmallGraph {
+    uint32_t U, E, method, phases;
+    uint32_t closed_form;                     // directional: the closed form (the keys are pairwise distinct), else relaxation sweeps
+    uint32_t r1_words;                        // set by launch_small_graph
+    uint32_t *edges;                          // adjacency orients them in place
+    const uint32_t *ucounts, *urecs, *ulens;
+    const uint64_t *ufirst;
+    uint32_t *labels;
+    uint8_t *kept;
+    uint64_t base, window;
+    uint64_t *list_out;
+    unsigned long long *ctr64;
+    uint32_t *g_best;
+    uint8_t *g_state;
+};
+hipError_t launch_small_graph(SmallGraph A, KeyShape sh, hipStream_t st);
+
 // edit.hip -- Levenshtein neighbour search + contains
 hipError_t launch_len_present(const uint32_t *ulens, uint64_t U, KeyShape sh, uint8_t *len_present, hipStream_t st);
 hipError_t launch_edit_records(const uint32_t *urecs, const uint32_t *ulens, uint64_t U, KeyShape sh, uint32_t d,

@@ -111,6 +111,9 @@ typedef struct fqd_summary {
 #define FQD_ROUTE_COLLAPSE_SMALL  0x100000u /* collapse of an input under 65 536 reads without a sort: a workgroup per hash bin
                                             * with the bin's distinct keys in an LDS table, rows ordered by (bin, first
                                             * position) (small_collapse.hip)                                                 */
+#define FQD_ROUTE_GRAPH_SMALL     0x200000u /* components, dissection and the kept-id list of a table of up to 5 854 keys as
+                                            * ONE launch of one workgroup, everything in its LDS (small_graph.hip); set only
+                                            * when that kernel's results are the ones kept                                    */
 int fqd_get_route(const fqd_ctx *ctx, uint32_t *route);
 
 /* Packed-key geometry chosen by fqd_pack_keys (DESIGN.md "data layout"). */
@@ -558,7 +561,8 @@ int fqd_stage_times(fqd_ctx *ctx, float *ms /* FQD_T_COUNT */, uint32_t *launche
 #define FQD_K_FASTQ_EMIT_SIZES   26   /* the FASTQ emit: output size of every kept record of a chunk, */
 #define FQD_K_FASTQ_EMIT_COPY    27   /* the output bytes, a tile per workgroup */
 #define FQD_K_SMALL_COLLAPSE     28   /* the collapse of a small input, both launches (small_collapse.hip) */
-#define FQD_K_COUNT         29
+#define FQD_K_SMALL_GRAPH        29   /* the graph stage of a small table in one launch (small_graph.hip) */
+#define FQD_K_COUNT         30
 int fqd_kernel_times(fqd_ctx *ctx, float *ms /* FQD_K_COUNT */, uint32_t *launches /* FQD_K_COUNT */,
                      int reset);
 /* What is timed. Timers never synchronise the host: they are event pairs recorded while the work
