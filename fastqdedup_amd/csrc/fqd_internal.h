@@ -693,6 +693,15 @@ hipError_t launch_group_crowded_tiles(const uint32_t *items, const uint32_t *buc
                                       uint32_t fused_U, uint32_t seg0, const uint32_t *urecs, const uint32_t *ulens, KeyShape sh,
                                       uint32_t d, uint32_t nseg, uint32_t *edges, unsigned long long *edge_count,
                                       uint64_t edge_cap, hipStream_t st, PairStats *stats = nullptr);
+// group_tiles_wide.hip -- the tiles for the shapes launch_group_crowded_tiles's own kernel refuses: records of up to 16
+// uint4 (any count), 1 to 4 planes. Called by launch_group_crowded_tiles, behind its gp_tile_prefix_kernel.
+bool group_wide_tiles_possible(KeyShape sh, uint32_t nseg);
+hipError_t launch_group_wide_tiles(const uint32_t *items, const uint32_t *bucket_start, const uint32_t *bucket_end,
+                                   const uint32_t *list, const unsigned long long *counts,
+                                   const unsigned long long *tile_prefix, uint32_t fused_U, uint32_t seg0,
+                                   const uint32_t *urecs, const uint32_t *ulens, KeyShape sh, uint32_t d, uint32_t nseg,
+                                   uint32_t *edges, unsigned long long *edge_count, uint64_t edge_cap, hipStream_t st,
+                                   PairStats *stats);
 hipError_t launch_group_verify_refined(const uint64_t *cands, const unsigned long long *cand_count, uint64_t cand_cap,
                                        const uint32_t *urecs, const uint32_t *ulens, KeyShape sh, uint32_t nseg,
                                        const uint32_t *seg_hashes, uint64_t U, uint32_t bucket_bits,

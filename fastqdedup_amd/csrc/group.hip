@@ -1372,7 +1372,8 @@ hipError_t launch_group_refine_items(const uint32_t *items, const uint32_t *buck
 }
 
 // all pairs of the crowded buckets (marked by launch_group_mark_crowded; list / counts from there), tiled:
-// tile_prefix has room for n_buckets + 1 words of 8 bytes. Records of up to 32 words; nseg <= 8.
+// tile_prefix has room for n_buckets + 1 words of 8 bytes. Records of 1, 2, 4 or 8 uint4 on 2 or 3 planes take the kernel
+// above; every other record of up to 64 words on 1 to 4 planes takes gp_wide_tiles_kernel (group_tiles_wide.hip). nseg <= 8.
 hipError_t launch_group_crowded_tiles(const uint32_t *items, const uint32_t *bucket_start, const uint32_t *bucket_end,
                                       const uint32_t *list, const unsigned long long *counts, unsigned long long *tile_prefix,
                                       uint32_t fused_U, uint32_t seg0, const uint32_t *urecs, const uint32_t *ulens, KeyShape sh,
@@ -1380,9 +1381,13 @@ hipError_t launch_group_crowded_tiles(const uint32_t *items, const uint32_t *buc
                                       uint64_t edge_cap, hipStream_t st, PairStats *stats)
 {
     const uint32_t q4 = sh.stride / 4;
-    if (sh.stride > 32 || (sh.stride & 3u) || (q4 & (q4 - 1)) || nseg > 8 || sh.planes < 2 || sh.planes > 3)
+    const bool wide = sh.stride > 32 || (sh.stride & 3u) || (q4 & (q4 - 1)) || nseg > 8 || sh.planes < 2 || sh.planes > 3;
+    if (wide && !group_wide_tiles_possible(sh, nseg))
         return hipErrorInvalidValue;
     gp_tile_prefix_kernel<<<1, 64, 0, st>>>(bucket_start, bucket_end, list, counts, tile_prefix);
+    if (wide)
+        return launch_group_wide_tiles(items, bucket_start, bucket_end, list, counts, tile_prefix, fused_U, seg0, urecs,
+                                       ulens, sh, d, nseg, edges, edge_count, edge_cap, st, stats);
 #define FQD_TILES(KK, QQ)                                                                                               \
     gp_crowded_tiles_kernel<KK, QQ><<<8192, CT_TS, 0, st>>>(reinterpret_cast<const uint2 *>(items), bucket_start,      \
                                                             bucket_end, list, counts, tile_prefix, fused_U, seg0, urecs, \
@@ -1400,7 +1405,8 @@ hipError_t launch_group_crowded_tiles(const uint32_t *items, const uint32_t *buc
 bool group_tiles_possible(KeyShape sh, uint32_t nseg)
 {
     const uint32_t q4 = sh.stride / 4;
-    return sh.stride <= 32 && !(sh.stride & 3u) && !(q4 & (q4 - 1)) && nseg <= 8 && sh.planes >= 2 && sh.planes <= 3;
+    return (sh.stride <= 32 && !(sh.stride & 3u) && !(q4 & (q4 - 1)) && nseg <= 8 && sh.planes >= 2 && sh.planes <= 3) ||
+           group_wide_tiles_possible(sh, nseg);
 }
 
 hipError_t launch_group_verify_refined(const uint64_t *cands, const unsigned long long *cand_count, uint64_t cand_cap,

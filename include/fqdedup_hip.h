@@ -101,7 +101,9 @@ typedef struct fqd_summary {
 #define FQD_ROUTE_ONE_KERNEL_COLLAPSE 0x8000u /* dedupe + compaction (+ search pass 0) of the compact records ran as ONE
                                             * persistent kernel: no tmp rows between the LDS table and the unique table   */
 #define FQD_ROUTE_SEARCH_TILES    0x10000u /* crowded segment values that the finer segments could not split (a family
-                                            * varying inside one piece) were compared ALL PAIRS, tiled over the GPU         */
+                                            * varying inside one piece) were compared ALL PAIRS, tiled over the GPU: records
+                                            * of up to 64 words (256 bytes, any multiple of 4 words) on 1 to 4 bit planes,
+                                            * at most 8 segments (d <= 7); longer rows and larger alphabets never set it    */
 #define FQD_ROUTE_SEARCH_SMALL    0x20000u /* neighbour search of a table under 65 536 keys: every pass in ONE launch, the
                                             * keys grouped by segment hash in LDS tables, no sort (small_search.hip)        */
 #define FQD_ROUTE_SEARCH_SMALL_EDIT 0x40000u /* Levenshtein search (d = 1..3) of a table under 32 768 keys: index and probe
